@@ -7,8 +7,16 @@ Workload (BASELINE.json metric / configs[1]; SURVEY 8d "C2"): Cornell box +
 MAX_BOUNCE_DEPTH 4.  Synthetic scene data (procedural mesh stand-ins; the
 reference's OBJ assets do not exist), the reference's real 1k HDR.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: it builds and
+uploads the scene, warms up, times the K steps, writes the accumulated image
+under --dump-outputs DIR if asked, and prints the line (value, ms_per_step).
+Everything else described below -- the live PMC passes, the PNRT_SERIAL steps
+behind the roofline's exclusive kernel times, the CPU leg with its parity check
+and CPU baselines, the GPU BVH-build timing -- runs only with --full; without it
+those fields of the line are null.
 
 N > 1: one process per GPU; the image rows are dealt in 8-row bands
 (rank r owns bands b with b % N == r), each rank renders its rows, and the
@@ -121,6 +129,15 @@ def parse(argv=None):
     ap.add_argument("--serial", action="store_true",
                     help="time the steps themselves with PNRT_SERIAL (one call in flight): for the rocprofv3 "
                          "--stats run whose trace-kernel average is the roofline's exclusive kernel_ms")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the live PMC passes, the PNRT_SERIAL steps "
+                         "(exclusive kernel times, roofline), the CPU leg (parity check, CPU baselines) and the GPU "
+                         "BVH-build timing.  Without it a run sets up, warms up, times the steps and prints the line "
+                         "(as --no-pmc --no-parity --serial-steps 0)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what they computed -- the accumulated image a caller reads "
+                         "back after the last step -- to DIR/accum.npy (float32; at most 64 MB: a fixed seeded "
+                         "sample of the rows of a larger image)")
     ap.add_argument("--save-image", default="")
     ap.add_argument("--spp", type=int, default=0, help="experiment: samples per step other than the config's 4")
     ap.add_argument("--iters-per-call", type=int, default=0,
@@ -137,7 +154,30 @@ def parse(argv=None):
                     help="process-group backend for N>1 (nccl = RCCL over xGMI; gloo = host-staged rehearsal)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)   # a PMC pass's workload: no output
     ap.add_argument("--shard-world", type=int, default=1, help=argparse.SUPPRESS)   # child: rank 0's share of N
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:              # a plain run: only what the headline figure needs
+        args.no_pmc = args.no_parity = True
+        args.serial_steps = 0
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_SEED = 20240521           # ... a larger image is sampled by rows drawn with this seed
+
+
+def dump_outputs(d: str, image) -> None:
+    """--dump-outputs: the timed path's output after its last step -- the accumulated
+    image (H x W x 4 float32: summed radiance and the sample count) that a caller reads
+    back with pnrt_read_accum -- as d/accum.npy.  An image above DUMP_MAX_BYTES (C5's 4K
+    frame) is cut to a fixed sample of its rows: as many as fit, drawn once with
+    DUMP_SEED, in ascending order -- the same rows for the same image shape."""
+    os.makedirs(d, exist_ok=True)
+    a = np.ascontiguousarray(image, dtype=np.float32)
+    fit = DUMP_MAX_BYTES // max(1, a[0].nbytes)
+    if fit < a.shape[0]:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], size=fit, replace=False))
+        a = np.ascontiguousarray(a[rows])
+    np.save(os.path.join(d, "accum.npy"), a)
 
 
 def log(*a):
@@ -777,10 +817,12 @@ def main(argv=None):
     # the timed image itself (frames 0 .. (warmup + steps) * spp - 1), for the parity
     # check of the CPU leg below; read before the PNRT_SERIAL steps add frames to it
     timed_image = None
-    if rank == 0 and (args.save_image or not args.no_parity):
+    if rank == 0 and (args.save_image or args.dump_outputs or not args.no_parity):
         timed_image = image.cpu().numpy() if world > 1 else pt.read_accum()
     if args.save_image and rank == 0:
         np.save(args.save_image, timed_image)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_image)
 
     # exclusive kernel times: PNRT_SERIAL steps (one call in flight, full trace grid)
     excl = {}
@@ -813,7 +855,7 @@ def main(argv=None):
         # the GPU (pnrt_bvh_build, incl. PCIe; same arrays), and the upload (pnrt_*)
         setup = {"scene_build_s": round(scene_s, 3), "bvh_build_host_s": round(cfg.packed.bvh_seconds, 4),
                  "upload_s": round(upload_s, 3)}
-        if cfg.packed.tri_bounds is not None:
+        if args.full and cfg.packed.tri_bounds is not None:
             tb = cfg.packed.tri_bounds
             pt.build_bvh(tb[: min(len(tb), 4096)])                    # module / allocation warm-up
             t = time.perf_counter()

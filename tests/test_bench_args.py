@@ -185,6 +185,41 @@ def test_issue_stats_and_valu_bound():
     assert b.derive_bound(0.27, 0.5, 0.4, 0.87, None) == "hbm-latency"
 
 
+def test_plain_run_is_lean_and_full_restores_the_rest():
+    """Without --full a run does only what the headline figure needs: no PMC passes,
+    no PNRT_SERIAL steps, no CPU leg -- whatever else is asked; --full leaves every
+    option as given (the defaults: all of them on)."""
+    b = _bench()
+    for argv in ([], ["--gpus", "1", "--steps", "5", "--warmup", "2"], ["--serial-steps", "3"]):
+        a = b.parse(argv)
+        assert not a.full and a.no_pmc and a.no_parity and a.serial_steps == 0, argv
+    a = b.parse(["--full"])
+    assert a.full and not a.no_pmc and not a.no_parity and not a.no_cpu_baseline and a.serial_steps == 2
+    a = b.parse(["--full", "--no-pmc", "--serial-steps", "0"])
+    assert a.no_pmc and not a.no_parity and a.serial_steps == 0
+    a = b.parse(["--steps", "7", "--dump-outputs", "d"])
+    assert a.steps == 7 and a.dump_outputs == "d" and b.parse([]).dump_outputs == ""
+
+
+def test_dump_outputs_whole_image_or_a_fixed_row_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the accumulated image as float32 accum.npy, bit for bit; an image
+    above the size limit is cut to the same seeded ascending row sample every time."""
+    import numpy as np
+    b = _bench()
+    img = np.random.default_rng(1).random((37, 11, 4), dtype=np.float32)
+    b.dump_outputs(str(tmp_path / "a"), img)
+    got = np.load(tmp_path / "a" / "accum.npy")
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), img.view(np.uint32))
+    assert 3840 * 2160 * 16 > b.DUMP_MAX_BYTES >= 1920 * 1080 * 16 and b.DUMP_MAX_BYTES <= 64 << 20
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 10 * img[0].nbytes + 5)
+    b.dump_outputs(str(tmp_path / "b"), img)
+    b.dump_outputs(str(tmp_path / "c"), img)
+    x, y = np.load(tmp_path / "b" / "accum.npy"), np.load(tmp_path / "c" / "accum.npy")
+    assert x.shape == (10, 11, 4) and x.nbytes <= b.DUMP_MAX_BYTES and np.array_equal(x.view(np.uint32), y.view(np.uint32))
+    rows = [int(np.flatnonzero((img == r).all(axis=(1, 2)))[0]) for r in x]
+    assert rows == sorted(set(rows))
+
+
 def test_batch_frames_match_the_library():
     """bench.BATCH_FRAMES_MAX / BATCH_SLOTS (the call plan's one-batch limits) are the
     library's WF_MAX_CHUNK_FRAMES / 2^WF_SLOT_BITS: a plan computed against a larger

@@ -14,7 +14,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_two_ranks_gather_equals_one(tmp_path):
-    args = ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--config", "C4"]
+    args = ["--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--config", "C4"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     a, b = str(tmp_path / "n1.npy"), str(tmp_path / "n2.npy")
     subprocess.run([sys.executable, "bench.py", *args, "--save-image", a], cwd=REPO, env=env, check=True,
@@ -33,7 +33,8 @@ def test_eight_gloo_ranks_gather_equals_one(tmp_path):
     rehearsed with 8 gloo ranks on the box's one GPU: the gathered C2 image
     equals the N = 1 image bit for bit, and each run's own parity check (the
     CPU leg's oracle rows of its timed image) passes (VERDICT r3 "Next" 8)."""
-    args = ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-pmc", "--serial-steps", "1", "--config", "C2"]
+    args = ["--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-pmc", "--serial-steps", "1", "--config",
+            "C2"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     a, b = str(tmp_path / "n1.npy"), str(tmp_path / "n8.npy")
     subprocess.run([sys.executable, "bench.py", *args, "--save-image", a], cwd=REPO, env=env, check=True,
@@ -57,7 +58,7 @@ def test_bench_self_launch_gloo_two_ranks(tmp_path):
     the line says n_gpus 2, carries live PMC traffic (rank 0's share, profiled
     before it joined the group), its own parity check passes, and the gathered
     image equals the N = 1 image bit for bit."""
-    base = ["--steps", "1", "--warmup", "1", "--config", "C2", "--serial-steps", "1"]
+    base = ["--full", "--steps", "1", "--warmup", "1", "--config", "C2", "--serial-steps", "1"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     a, b = str(tmp_path / "n1.npy"), str(tmp_path / "n2.npy")
@@ -133,7 +134,8 @@ def test_rccl_gather_two_ranks_one_gpu(tmp_path):
 def test_bench_iters_per_call_same_image(tmp_path):
     """bench.py --iters-per-call 2 renders two 4-spp iterations per pnrt_render
     call (and per gather): the accumulated image equals one call per iteration."""
-    args = ["--steps", "2", "--warmup", "2", "--no-cpu-baseline", "--no-pmc", "--serial-steps", "0", "--config", "C4"]
+    args = ["--full", "--steps", "2", "--warmup", "2", "--no-cpu-baseline", "--no-pmc", "--serial-steps", "0", "--config",
+            "C4"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     a, b = str(tmp_path / "ipc1.npy"), str(tmp_path / "ipc2.npy")
     for out, ipc in ((a, "1"), (b, "2")):

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=${2:-gpurun_out/pmcdiag}
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS=${BENCH_ARGS:-"--steps 2 --warmup 1 --no-cpu-baseline"}
+ARGS=${BENCH_ARGS:-"--full --steps 2 --warmup 1 --no-cpu-baseline"}
 i=0
 while IFS= read -r grp; do
   [ -z "$grp" ] && continue

@@ -2,7 +2,7 @@
 # One GPU-box session (rounds 4-5), steps chosen by STEPS (space-separated, in order):
 #   smoke    __graft_entry__.smoke()
 #   tests    the whole -m gpu suite (TESTS= to narrow it, e.g. TESTS="tests/test_gpu_parity.py")
-#   bench    bench.py C2 default (live PMC, CPU leg with the parity check)   [CONFIGS= for others]
+#   bench    bench.py --full C2 (live PMC, CPU leg with the parity check)   [CONFIGS= for others]
 #   d2       the reference's dispatch shape D2 / D3, pipelined and synchronised per frame (no HIP events;
 #            + a synchronised run with every kernel timed)
 #   ab       A/B of prebuilt variants (VARIANTS="name ...", ROUNDS=n): C2 (+ AB_CONFIGS) per variant
@@ -68,18 +68,18 @@ for s in ${STEPS:-smoke tests bench}; do
     bench)
       for c in ${CONFIGS:-C2}; do
         extra=""; [ $c = C5 ] && extra="--steps 10"; [ $c != C2 ] && extra="$extra --cpu-seconds 6"
-        step bench-$c timeout -k 10 600 python bench.py --config $c $extra ${BENCH_ARGS:-} > $O/bench_$c.json 2> $O/bench_$c.err
+        step bench-$c timeout -k 10 600 python bench.py --full --config $c $extra ${BENCH_ARGS:-} > $O/bench_$c.json 2> $O/bench_$c.err
         summ $O/bench_$c.json
       done ;;
     d2)        # the headline lines without HIP events (an event pair around each of a frame's 10
                # launches costs ~12 % of a synchronised 512x512 frame); + one with every kernel timed
       for c in ${DCONFIGS:-D2 D3}; do
         for sync in "" "--sync-per-frame"; do
-          step $c$sync timeout -k 10 200 python bench.py --config $c $sync --steps 240 --warmup 16 --no-cpu-baseline \
+          step $c$sync timeout -k 10 200 python bench.py --full --config $c $sync --steps 240 --warmup 16 --no-cpu-baseline \
             --no-pmc --serial-steps 0 --no-kernel-events > $O/${c}${sync}.json 2> $O/${c}${sync}.err
           summ $O/${c}${sync}.json
         done
-        step $c-kt timeout -k 10 200 python bench.py --config $c --sync-per-frame --steps 240 --warmup 16 --no-cpu-baseline \
+        step $c-kt timeout -k 10 200 python bench.py --full --config $c --sync-per-frame --steps 240 --warmup 16 --no-cpu-baseline \
           --no-pmc --serial-steps 0 --kernel-times > $O/${c}--sync-per-frame-kernel-times.json 2> $O/${c}-kt.err
         summ $O/${c}--sync-per-frame-kernel-times.json
       done ;;
@@ -119,9 +119,9 @@ for s in ${STEPS:-smoke tests bench}; do
       done ;;
     prof)
       step prof-serial timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_serial -o run --output-format csv -- \
-        python bench.py --steps 20 --warmup 20 --no-cpu-baseline --no-pmc --serial > $O/prof_serial.json 2> $O/prof_serial.err
+        python bench.py --full --steps 20 --warmup 20 --no-cpu-baseline --no-pmc --serial > $O/prof_serial.json 2> $O/prof_serial.err
       step prof-pipe timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_pipe -o run --output-format csv -- \
-        python bench.py --steps 20 --warmup 20 --no-cpu-baseline --no-pmc > $O/prof_pipe.json 2> $O/prof_pipe.err
+        python bench.py --full --steps 20 --warmup 20 --no-cpu-baseline --no-pmc > $O/prof_pipe.json 2> $O/prof_pipe.err
       for m in serial pipe; do     # rocprof's trace-kernel average vs the line's kernel_ms (CPU only)
         python3 tools/prof_summary.py $O/prof_$m/run_kernel_trace.csv $O/prof_$m.json $O/prof_${m}_check.json > /dev/null \
           && python3 -c "import json; print('  prof-$m', json.load(open('$O/prof_${m}_check.json'))['check'])"
