@@ -49,6 +49,8 @@ typedef struct {
     int64_t device_bytes;/* scene bytes resident in HBM                      */
     int root_is_leaf;
     int stack_limit;     /* traversal stack entries available per lane       */
+    int has_leaf_table;  /* a leaf too large for an inline ref: the scene runs the */
+                         /* leaf-table instantiation of the trace kernels          */
 } pnrt_device_info;
 
 /* Options (pnrt_set_options): a traversal mode, optionally | a kernel variant. */
@@ -136,11 +138,31 @@ int pnrt_set_options(pnrt_ctx* ctx, int options);
  * y with (y / band_rows) % n_shards == shard are rendered; full image =
  * (band_rows >= 1, n_shards = 1, shard = 0).  Asynchronous on the stream.
  * The frames run in batches of up to 128 frames and 2^28 paths (~310 B of
- * device memory per path; the environment variable PNRT_BATCH_BYTES, read at a
- * context's first render, caps one batch's bytes -- the batching changes no
- * pixel). */
+ * device memory per path; the environment variable PNRT_BATCH_BYTES, read when
+ * the context is created, caps one batch's bytes -- the batching changes no
+ * pixel; pnrt_batch_plan reports it).
+ * Frame numbers end at 0xFFFFFFFE: frame 0xFFFFFFFF would blend with the weight
+ * 1 / (float)(frameCount + 1) = 1 / 0, and the frames after it would wrap to 0.
+ * A call with first_frame + n_frames > 0xFFFFFFFF returns PNRT_E_ARG, queues
+ * nothing and leaves the accumulation image untouched. */
 int pnrt_render(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames, int band_rows,
                 int n_shards, int shard);
+
+/* The batches pnrt_render would run for a call of n_frames frames with this
+ * shard selector at the current frame size (read-only, queues nothing; the
+ * PNRT_KERNEL_V1 path has no batches, the wavefront plan is reported all the
+ * same): frames per full batch, the number of batches (the last may be
+ * shorter), and batch_bytes, the measure PNRT_BATCH_BYTES caps -- the path
+ * state and colour bytes of one full batch.  Under a cap, frames_per_batch is
+ * the largest count whose batch_bytes fit it, and 1 when not even one frame
+ * does.  All three are 0 for n_frames = 0 or a shard with no rows.  Out
+ * pointers may be NULL.  PNRT_E_STATE before pnrt_set_frame.
+ *
+ * PNRT_BATCH_BYTES is read by pnrt_create: decimal digits only, a value that
+ * fits 64 bits, 0 = no cap.  Any other spelling ("3e9", "abc", "-1", "",
+ * trailing characters) makes pnrt_create return PNRT_E_ARG. */
+int pnrt_batch_plan(pnrt_ctx* ctx, uint32_t n_frames, int band_rows, int n_shards, int shard,
+                    uint32_t* frames_per_batch, uint32_t* n_batches, int64_t* batch_bytes);
 
 /* Redraw semantics (main.cpp:592-596): zero the accumulation image.  Waits
  * for the calls in flight first, and clears a PNRT_E_TRACE fault. */

@@ -84,7 +84,8 @@ class Camera(ctypes.Structure):
 class DeviceInfo(ctypes.Structure):
     _fields_ = [("n_interior", ctypes.c_int), ("n_triangles", ctypes.c_int),
                 ("max_depth", ctypes.c_int), ("device_bytes", ctypes.c_int64),
-                ("root_is_leaf", ctypes.c_int), ("stack_limit", ctypes.c_int)]
+                ("root_is_leaf", ctypes.c_int), ("stack_limit", ctypes.c_int),
+                ("has_leaf_table", ctypes.c_int)]
 
 
 K_CLASSES = ("primary", "gen", "setup", "trace", "shade", "blend", "v1")   # PNRT_K_* order
@@ -136,6 +137,8 @@ def _type_device(lib):
     _sig(lib, "pnrt_set_frame", INT, P, INT, INT, ctypes.POINTER(Camera), INT)
     _sig(lib, "pnrt_set_options", INT, P, INT)
     _sig(lib, "pnrt_render", INT, P, ctypes.c_uint32, ctypes.c_uint32, INT, INT, INT)
+    _sig(lib, "pnrt_batch_plan", INT, P, ctypes.c_uint32, INT, INT, INT, ctypes.POINTER(ctypes.c_uint32),
+         ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int64))
     _sig(lib, "pnrt_reset_accum", INT, P)
     _sig(lib, "pnrt_read_accum", INT, P, F)
     _sig(lib, "pnrt_accum_device_ptr", P, P)

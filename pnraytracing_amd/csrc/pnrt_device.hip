@@ -512,16 +512,49 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
     return PNRT_OK;
 }
 
+// PNRT_BATCH_BYTES: decimal digits only, a value that fits 64 bits (0: no cap).
+// Anything else -- "3e9", "abc", "-1", "", trailing junk -- is refused, not guessed at.
+static bool parse_batch_bytes(const char* s, uint64_t* out) {
+    if (!s || !*s) return false;
+    uint64_t v = 0;
+    for (; *s; ++s) {
+        if (*s < '0' || *s > '9') return false;
+        const uint64_t d = (uint64_t)(*s - '0');
+        if (v > (UINT64_MAX - d) / 10) return false;
+        v = v * 10 + d;
+    }
+    *out = v;
+    return true;
+}
+
+// Path slots of one frame of `rows` rows (8x8-pixel tiles) and the bytes the cap
+// measures for a batch of k such frames: the wavefront buffers and the colours.
+static size_t frame_paths(int width, int rows) {
+    return (size_t)((width + 7) / 8) * (size_t)((rows + 7) / 8) * 64;
+}
+static size_t batch_bytes(size_t per_frame, size_t pix, uint32_t k) {
+    return wf_bytes(per_frame * k) + pix * 16 * k;
+}
+// Frames per batch of a call of nf frames (the one plan: render_wavefront and
+// pnrt_batch_plan): at most WF_MAX_CHUNK_FRAMES, few enough that every path slot
+// fits the path state's slot field (large frames take fewer per batch), and under
+// PNRT_BATCH_BYTES the largest count whose batch_bytes fit the cap -- one frame when
+// not even one does.  0: a frame too large for one batch.
+static uint32_t plan_chunk(const pnrt_ctx* c, size_t per_frame, size_t pix, uint32_t nf) {
+    if (per_frame == 0 || per_frame > (size_t)WF_META_SLOT) return 0;
+    const uint32_t fit = (uint32_t)std::min<size_t>(WF_MAX_CHUNK_FRAMES, (size_t)WF_META_SLOT / per_frame);
+    uint32_t chunk = nf < fit ? nf : fit;
+    // (batch_bytes grows with the frame count, so the first count that fits is the largest)
+    while (c->batch_bytes_cap && chunk > 1 && batch_bytes(per_frame, pix, chunk) > c->batch_bytes_cap) --chunk;
+    return chunk;
+}
+
 static int pipes_init(pnrt_ctx* c) {
     if (c->pipes_ready) return PNRT_OK;
     c->pipes_ready = true;
     const char* q = getenv("GPU_MAX_HW_QUEUES");
     const int hw_queues = (q && atoi(q) > 0) ? atoi(q) : 4;
     c->n_pipes_small = hw_queues > 4 ? WF_PIPES : WF_PIPES_LARGE;
-    // a caller short of device memory (another tenant, a smaller part) caps one batch's
-    // buffers; frames per batch shrink to fit, which changes no pixel
-    const char* bb = getenv("PNRT_BATCH_BYTES");
-    c->batch_bytes_cap = bb ? (size_t)strtoull(bb, nullptr, 10) : 0;
     for (unsigned i = 0; i < c->n_pipes_small; ++i) {
         auto& P = c->pipe[i];
         HIPCHK(c, hipStreamCreateWithFlags(&P.w, hipStreamNonBlocking));
@@ -542,17 +575,10 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
     int rc;
     if ((rc = pipes_init(c))) return rc;
     const size_t pix = (size_t)fp.rows * c->width;
-    const int tiles_x = (c->width + 7) / 8, tiles_y = (fp.rows + 7) / 8;
-    const size_t per_frame = (size_t)tiles_x * tiles_y * 64;
-    // frames per batch: at most WF_MAX_CHUNK_FRAMES, and few enough that every path
-    // slot fits the path state's slot field (large frames take fewer per batch)
-    if (per_frame > (size_t)WF_META_SLOT) return set_err(c, PNRT_E_ARG, "render: frame too large for one batch");
-    const uint32_t fit = (uint32_t)std::min<size_t>(WF_MAX_CHUNK_FRAMES, (size_t)WF_META_SLOT / per_frame);
-    uint32_t chunk = nf < fit ? nf : fit;
-    // (PNRT_BATCH_BYTES: one batch's path state and colours within the cap, down to one frame)
-    while (c->batch_bytes_cap && chunk > 1 &&
-           wf_bytes(per_frame * chunk) + pix * 16 * chunk > c->batch_bytes_cap)
-        chunk = (chunk + 1) / 2;
+    const int tiles_x = (c->width + 7) / 8;
+    const size_t per_frame = frame_paths(c->width, fp.rows);
+    const uint32_t chunk = plan_chunk(c, per_frame, pix, nf);   // frames per batch
+    if (chunk == 0) return set_err(c, PNRT_E_ARG, "render: frame too large for one batch");
     // calls in flight by call size (paths per batch): small (< 5M: multi-GPU shares)
     // 4 with > 4 hardware queues; 5M-12M 2 -- their launches are long enough to fill
     // each other's drains (measured on 8-frame 1080p calls before the staggering: C2
@@ -698,10 +724,18 @@ const char* pnrt_version(void) {
 int pnrt_create(int device, pnrt_ctx** out) {
     if (!out) return PNRT_E_ARG;
     *out = nullptr;
+    // a caller short of device memory (another tenant, a smaller part) caps one batch's
+    // buffers; frames per batch shrink to fit, which changes no pixel.  Read here, once,
+    // and strictly: a misspelt cap must not turn into a 3-byte cap or into none
+    // (there is no context yet to carry a message: the code is the report)
+    uint64_t cap = 0;
+    const char* bb = getenv("PNRT_BATCH_BYTES");
+    if (bb && !parse_batch_bytes(bb, &cap)) return PNRT_E_ARG;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return PNRT_E_HIP;
     pnrt_ctx* c = new pnrt_ctx();
     c->device = device;
+    c->batch_bytes_cap = (size_t)cap;
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return PNRT_E_HIP;
@@ -1239,6 +1273,10 @@ int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int
     if (!c) return PNRT_E_ARG;
     if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, "render: upload_scene and set_frame first");
     if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "render: bad shard selector");
+    // frame 0xFFFFFFFF has the blend weight 1 / (float)0 (frameCount + 1 wraps), and the
+    // frames after it would restart at 0: refused before anything is queued
+    if ((uint64_t)first + nf > 0xFFFFFFFFull)
+        return set_err(c, PNRT_E_ARG, "render: first_frame + n_frames exceeds 0xFFFFFFFF (the last frame number is 0xFFFFFFFE)");
     if (int rc = check_fault(c)) return rc;      // an earlier call's trace fault (completed work)
     if (nf == 0) return PNRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1278,6 +1316,27 @@ int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int
         return mark_stream(c);           // (every op queued on c->stream records ev_last)
     }
     return render_wavefront(c, s, fp, first, nf);
+}
+
+int pnrt_batch_plan(pnrt_ctx* c, uint32_t nf, int band, int nsh, int shard, uint32_t* frames_per_batch,
+                    uint32_t* n_batches, int64_t* bytes) {
+    if (!c) return PNRT_E_ARG;
+    if (!c->has_frame) return set_err(c, PNRT_E_STATE, "batch_plan: set_frame first");
+    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "batch_plan: bad shard selector");
+    uint32_t chunk = 0, nb = 0;
+    int64_t by = 0;
+    const int rows = shard_rows(c->height, band, nsh, shard);
+    if (nf > 0 && rows > 0) {                    // (pnrt_render queues nothing otherwise)
+        const size_t per_frame = frame_paths(c->width, rows), pix = (size_t)rows * c->width;
+        chunk = plan_chunk(c, per_frame, pix, nf);
+        if (chunk == 0) return set_err(c, PNRT_E_ARG, "batch_plan: frame too large for one batch");
+        nb = nf / chunk + (nf % chunk ? 1u : 0u);
+        by = (int64_t)batch_bytes(per_frame, pix, chunk);
+    }
+    if (frames_per_batch) *frames_per_batch = chunk;
+    if (n_batches) *n_batches = nb;
+    if (bytes) *bytes = by;
+    return PNRT_OK;
 }
 
 int pnrt_reset_accum(pnrt_ctx* c) {
@@ -1377,6 +1436,7 @@ int pnrt_get_device_info(pnrt_ctx* c, pnrt_device_info* info) {
     info->device_bytes = c->scene_bytes;
     info->root_is_leaf = c->root_is_leaf;
     info->stack_limit = PT_STACK;
+    info->has_leaf_table = c->scene.has_leaf_table ? 1 : 0;
     return PNRT_OK;
 }
 

@@ -8,6 +8,7 @@ All compute runs in the HIP library; if it is missing this module raises.
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 
@@ -29,6 +30,9 @@ class PathTracer:
         self._lib = N.device_lib()
         ctx = ctypes.c_void_p()
         rc = self._lib.pnrt_create(device, ctypes.byref(ctx))
+        if rc == -1:     # PNRT_E_ARG: the only argument besides the device is the environment's cap
+            raise PnrtError(f"pnrt_create(device={device}) failed ({rc}): PNRT_BATCH_BYTES="
+                            f"{os.environ.get('PNRT_BATCH_BYTES')!r} is not a decimal byte count")
         if rc != 0:
             raise PnrtError(f"pnrt_create(device={device}) failed ({rc}): no usable HIP device")
         self._ctx = ctx
@@ -132,7 +136,22 @@ class PathTracer:
 
     # ---- frames ----------------------------------------------------------------------
     def render(self, first_frame: int, n_frames: int, band: int = 1, n_shards: int = 1, shard: int = 0):
+        # (ctypes would truncate 2**32 + 5 to 5 without a word)
+        for name, v in (("first_frame", first_frame), ("n_frames", n_frames)):
+            if not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError(f"render: {name} = {v} is outside 0 .. 2**32 - 1")
         self._ck(self._lib.pnrt_render(self._ctx, first_frame, n_frames, band, n_shards, shard), "pnrt_render")
+
+    def batch_plan(self, n_frames: int, band: int = 1, n_shards: int = 1, shard: int = 0) -> dict:
+        """The batches ``render`` would run for such a call at the current frame size
+        (pnrt_batch_plan): frames per full batch, number of batches, and the bytes of one
+        full batch as PNRT_BATCH_BYTES measures them."""
+        if not 0 <= n_frames <= 0xFFFFFFFF:
+            raise ValueError(f"batch_plan: n_frames = {n_frames} is outside 0 .. 2**32 - 1")
+        fpb, nb, by = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int64()
+        self._ck(self._lib.pnrt_batch_plan(self._ctx, n_frames, band, n_shards, shard, ctypes.byref(fpb),
+                                           ctypes.byref(nb), ctypes.byref(by)), "pnrt_batch_plan")
+        return {"frames_per_batch": fpb.value, "n_batches": nb.value, "batch_bytes": by.value}
 
     def reset_accum(self):
         self._ck(self._lib.pnrt_reset_accum(self._ctx), "pnrt_reset_accum")

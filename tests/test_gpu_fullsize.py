@@ -175,17 +175,30 @@ def test_batch_beyond_2_26_paths(pt):
 
 
 def test_batch_bytes_cap(pt):
-    """PNRT_BATCH_BYTES (read when a context first renders) caps one batch's device
-    buffers: a 40-frame C4 call then runs in 14 batches of at most 3 frames
-    (≈ 0.64 GB per 1080p frame) and equals the one-batch call bit for bit."""
+    """PNRT_BATCH_BYTES (read when a context is created) caps one batch's device
+    buffers: a 40-frame C4 call then runs in 10 batches of 4 frames (0.643 GB per
+    1080p frame, bytes(4) = 2 571 919 680: the most that fit 3 GB, worked out here
+    from the uncapped context's own pnrt_batch_plan), launches one gen kernel per
+    batch, and equals the one-batch call bit for bit."""
     import os
     c = cfg("C4")
+    cap = 3 * 10**9
     one = gpu_render(pt, c, 0, 40)
-    os.environ["PNRT_BATCH_BYTES"] = str(3 * 10**9)
+    by = [pt.batch_plan(k)["batch_bytes"] for k in range(1, 41)]          # by[k - 1] = bytes(k), no cap
+    assert pt.batch_plan(40) == {"frames_per_batch": 40, "n_batches": 1, "batch_bytes": by[39]}
+    fit = max([k for k in range(1, 41) if by[k - 1] <= cap], default=1)
+    assert 1 < fit < 40, "the cap must bite, and leave room for more than one frame"
+    os.environ["PNRT_BATCH_BYTES"] = str(cap)
     capped = PathTracer(0)
     try:
-        got = gpu_render(capped, c, 0, 40)
+        capped.load(c)
+        plan = capped.batch_plan(40)
+        capped.profile_enable(True)
+        got = gpu_render(capped, c, 0, 40, load=False)
+        gen = capped.profile_read()["gen"][1]
     finally:
         capped.close()
         del os.environ["PNRT_BATCH_BYTES"]
-    assert_bitwise(got, one, "C4 40 frames: 3-frame batches (PNRT_BATCH_BYTES) vs one batch")
+    assert plan == {"frames_per_batch": fit, "n_batches": -(-40 // fit), "batch_bytes": by[fit - 1]}
+    assert gen == plan["n_batches"]
+    assert_bitwise(got, one, "C4 40 frames: capped batches (PNRT_BATCH_BYTES) vs one batch")

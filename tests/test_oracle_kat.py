@@ -27,6 +27,44 @@ def test_sobol_first_point_is_half():
     assert all(L.pno_sobol(d, 1) == 0.5 for d in range(8))
 
 
+def _gray(i):
+    return i ^ (i >> 1)
+
+
+def _sobol_indices():
+    idx = [1 << j for j in range(32)] + [0xFFFFFFFF]
+    for k in (8, 16, 24, 31):                     # grayCode(frameCount + 1) around a new top bit
+        idx += [_gray(2**k - 1), _gray(2**k), _gray(2**k + 1)]
+    rng = np.random.default_rng(20)
+    return idx + [int(v) for v in rng.integers(0, 2**32, 1000, dtype=np.uint64)]
+
+
+def test_sobol_matches_integer_reference():
+    """pno_sobol(d, i) for all 8 dimensions against an integer reference built from
+    the committed direction table (tests/golden/sobol_v.json): the XOR of the
+    table entries of i's set bits in Python ints, then the shader's one float
+    multiply -- exactly, for every single bit (bits 8..31 are the ones frame
+    numbers above 255 set), all bits, the gray codes around 2^8, 2^16, 2^24 and
+    2^31, and 1000 random 32-bit indices."""
+    import json
+    import os
+    V = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "sobol_v.json")))["V"]
+    assert len(V) == 256 and all(0 <= v < 2**32 for v in V)
+    L = pyoracle.lib()
+    scale = np.float32(1) / np.float32(0xFFFFFFFF)
+    for d in range(8):
+        for i in _sobol_indices():
+            r = 0
+            for j in range(32):
+                if (i >> j) & 1:
+                    r ^= V[32 * d + j]
+            want = np.float32(r) * scale
+            got = np.float32(L.pno_sobol(d, i))
+            assert got.view(np.uint32) == want.view(np.uint32), (d, hex(i), got, want)
+    # a sample of exactly 1.0, outside [0, 1): the shader's own arithmetic, kept as it is
+    assert L.pno_sobol(1, 0x80000000) == 1.0
+
+
 def _ulps(a, b):
     a = np.asarray(a, np.float32).view(np.int32).astype(np.int64)
     b = np.asarray(b, np.float32).view(np.int32).astype(np.int64)
