@@ -84,7 +84,13 @@ void* pnrt_get_stream(pnrt_ctx* ctx);
  *   vertices  15 f each (main.cpp:412-428)     materials 18 f (main.cpp:438-456)
  *   triangles  6 f each (main.cpp:470-477)     bvh_nodes 12 f (main.cpp:488-501)
  *   lights     3 f each (main.cpp:513-517)     (lights may be NULL when n_lights = 0)
- * The arrays are validated and re-laid out for gfx950. */
+ * The arrays are validated and re-laid out for gfx950.
+ * A triangle's texture id (float 4 of its record) is -1 (no texture) or a slot
+ * 0..19 -- the reference binds 20 samplers, other ids are undefined there -- and
+ * any other id returns PNRT_E_SCENE naming the triangle.  A slot 0..19 that no
+ * pnrt_upload_texture call filled is legal: an unbound sampler, such a hit is
+ * black.  The BVH may be at most stack_limit - 2 levels deep (pnrt_device_info),
+ * its root may be a leaf, and a leaf may be empty (start == end). */
 int pnrt_upload_scene(pnrt_ctx* ctx,
                       const float* vertices, int n_vertices,
                       const float* materials, int n_materials,
@@ -136,7 +142,11 @@ int pnrt_set_options(pnrt_ctx* ctx, int options);
  * order into the accumulation image with the progressive mean of
  * ray_tracing.comp:988-991.  Shard selector (multi-GPU row bands): only rows
  * y with (y / band_rows) % n_shards == shard are rendered; full image =
- * (band_rows >= 1, n_shards = 1, shard = 0).  Asynchronous on the stream.
+ * (band_rows >= 1, n_shards = 1, shard = 0).  band_rows may be any positive int
+ * (up to INT_MAX; here and in pnrt_batch_plan, pnrt_pack_rows, pnrt_unpack_rows):
+ * with band_rows >= height the image is one band, shard 0 renders all of it and
+ * every other shard has no rows (the call returns PNRT_OK and queues nothing).
+ * Asynchronous on the stream.
  * The frames run in batches of up to 128 frames and 2^28 paths (~310 B of
  * device memory per path; the environment variable PNRT_BATCH_BYTES, read when
  * the context is created, caps one batch's bytes -- the batching changes no

@@ -877,6 +877,8 @@ int pnrt_upload_scene(pnrt_ctx* c, const float* V, int nv, const float* M, int n
             if (id[k] < 0 || id[k] >= nv) return set_err(c, PNRT_E_SCENE, "triangle " + std::to_string(i) + " has an out-of-range vertex index");
         int mat = fint(t[3]), tex = fint(t[4]);
         if (mat < 0 || mat >= nm) return set_err(c, PNRT_E_SCENE, "triangle " + std::to_string(i) + " has an out-of-range material id");
+        // the reference binds PT_MAX_TEXTURES samplers; the wavefront records keep tex + 1 in 8 bits
+        if (tex < -1 || tex >= PT_MAX_TEXTURES) return set_err(c, PNRT_E_SCENE, "triangle " + std::to_string(i) + " has an out-of-range texture id");
         const float* p0 = V + 15 * (size_t)id[0];
         const float* p1 = V + 15 * (size_t)id[1];
         const float* p2 = V + 15 * (size_t)id[2];
@@ -1264,9 +1266,12 @@ int pnrt_set_frame(pnrt_ctx* c, int w, int h, const pnrt_camera* cam, int depth)
 }
 
 static int shard_rows(int h, int band, int n, int shard) {
-    int rows = 0;
-    for (int y0 = shard * band; y0 < h; y0 += band * n) rows += (h - y0 < band) ? h - y0 : band;
-    return rows;
+    // 64-bit row positions: band may be any positive int (band >= h: one band), and
+    // shard * band or band * n leave int long before that
+    int64_t rows = 0;
+    const int64_t step = (int64_t)band * n;
+    for (int64_t y0 = (int64_t)shard * band; y0 < h; y0 += step) rows += (h - y0 < band) ? h - y0 : band;
+    return (int)rows;
 }
 
 int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int shard) {

@@ -234,6 +234,10 @@ PN_DEV f3 path_trace(const DevScene& s, const FrameParams& fp, Hit isect, f3 V, 
 }
 
 // Local row index -> image row for the shard (rows y with (y / band) % n == shard).
+// Only for a row the shard has (r < the host's shard_rows() count; every caller
+// masks its padding lanes first, or maps them to r = 0): the result is then below
+// the image height and no intermediate exceeds it, so int holds any band_rows and
+// n_shards up to INT_MAX.  A padded row must not come here: its product can wrap.
 PN_DEV int shard_row(int r, int band, int n_shards, int shard) {
     int blk = r / band;
     return (blk * n_shards + shard) * band + (r - blk * band);

@@ -61,6 +61,9 @@ def cases(which: str):
         for seed in range(int(os.environ.get("PNRT_COOP_SEEDS", "24"))):
             cfg, rng = random_scene(seed)
             out.append((f"fuzz{seed}", cfg, int(rng.integers(0, 20)), int(rng.integers(1, 10))))
+    if which == "limits":      # trees at the stack limit, root / empty leaves, sub-tile frames, rays in box faces
+        from test_gpu_limits import limit_cases
+        out += limit_cases()
     return out
 
 
