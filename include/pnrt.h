@@ -194,6 +194,65 @@ int pnrt_unpack_rows(pnrt_ctx* ctx, const void* src_device, void* image_device, 
 int pnrt_synchronize(pnrt_ctx* ctx);
 int pnrt_get_device_info(pnrt_ctx* ctx, pnrt_device_info* info);
 
+/* First-hit guide images (not in the reference, which shows the raw accumulation:
+ * main.cpp:618-628): what the un-jittered camera ray (ray_tracing.comp:205-211,
+ * 980) hits in every pixel, as three width*height RGBA32F images, row 0 = bottom
+ * -- the inputs of pnrt_denoise and of any external denoiser. */
+#define PNRT_AOV_POSITION 0   /* P.xyz of the camera ray's closest hit; w = 1 hit, 0 miss (xyz = 0) */
+#define PNRT_AOV_NORMAL   1   /* the shading normal of the hit (ray_tracing.comp:320-355, facing the ray, */
+                              /* normalised); w = (float)materialId, -1 on a miss (xyz = 0)               */
+#define PNRT_AOV_ALBEDO   2   /* hit: the baseColor the first bounce shades with (ray_tracing.comp:871:   */
+                              /* the bilinear REPEAT texture fetch at (u, v) when textureId != -1, else   */
+                              /* material.baseColor) -- or, on an emissive material (any emission         */
+                              /* component != 0), the emission; miss: the env colour of the primary       */
+                              /* direction (0 without an env); w = (float)textureId, -1 when none or on a */
+                              /* miss                                                                     */
+#define PNRT_AOV_COUNT 3
+/* Render the three images for the current frame size, camera, scene and
+ * traversal mode -- always the whole image, whatever shards pnrt_render is
+ * called with.  Asynchronous on the stream.  The per-pixel records pnrt_render
+ * keeps of the camera rays' hits are reused when a call in this context rendered
+ * the whole image with the same camera (then no ray is traced), and are never
+ * changed; otherwise the camera rays are traced into a buffer of the guides' own
+ * (one launch of class PNRT_K_PRIMARY).  PNRT_E_STATE before pnrt_upload_scene
+ * or pnrt_set_frame.  The buffers are allocated by the first call. */
+int pnrt_render_guides(pnrt_ctx* ctx);
+/* Synchronise and copy one guide image, width*height*4 floats (row 0 = bottom), to
+ * the host.  PNRT_E_STATE before pnrt_render_guides, or when the frame size has
+ * changed since. */
+int pnrt_read_aov(pnrt_ctx* ctx, int which, float* rgba_out);
+/* Device pointer of a guide image (NULL before the first pnrt_render_guides). */
+void* pnrt_aov_device_ptr(pnrt_ctx* ctx, int which);
+
+/* The denoised preview: the edge-avoiding a-trous wavelet filter (Dammertz et al.
+ * 2010) over the accumulation image divided by max(albedo, 1/256), guided by the
+ * normal and position images, multiplied by the albedo again -- a second image
+ * beside the accumulation image, which is read and never written.  `levels`
+ * passes (1..5); pass i = 0.. takes the 5x5 B3-spline taps at spacing 2^i, a tap
+ * weighing h * exp2(-(|dc|^2 / (sigma_color * 2^-i)^2 + |dn|^2 / sigma_normal^2 +
+ * |dp|^2 / sigma_position^2)); taps outside the image are skipped.  Misses and
+ * hits on emissive materials pass through: their pixels are the accumulation's,
+ * bit for bit, and they weigh 0 as taps.  Alpha is 1 elsewhere.  The result is
+ * defined bit for bit.
+ * Asynchronous on the stream: ordered after the blends of the pnrt_render calls
+ * already issued, and later calls are ordered after it.
+ * params == NULL: levels 5, sigma_color 2, sigma_normal 0.25, sigma_position 0.5.
+ * PNRT_E_ARG: levels outside 1..5, a sigma that is not finite and > 0 (the denoised
+ * image is left as it was).  PNRT_E_STATE: no guide images, or guide images that
+ * were rendered for another camera, frame size, scene (pnrt_upload_scene,
+ * pnrt_update_materials, pnrt_upload_texture, pnrt_upload_env*) or traversal mode
+ * -- call pnrt_render_guides again.  PNRT_E_TRACE as pnrt_pack_rows returns it. */
+typedef struct {
+    int levels;
+    float sigma_color, sigma_normal, sigma_position;
+} pnrt_denoise_params;
+int pnrt_denoise(pnrt_ctx* ctx, const pnrt_denoise_params* params);
+/* Synchronise and copy the denoised image (width*height*4 floats, row 0 = bottom). */
+int pnrt_read_denoised(pnrt_ctx* ctx, float* rgba_out);
+/* Device pointer of the denoised image (NULL before the first pnrt_denoise; the
+ * same pointer after every call at one frame size). */
+void* pnrt_denoised_device_ptr(pnrt_ctx* ctx);
+
 /* Per-kernel timing (not in the reference, which has no GPU timers): while
  * enabled, every launch of a kernel class is bracketed by HIP events recorded on
  * the launch stream; pnrt_profile_read synchronises and returns the summed

@@ -95,6 +95,17 @@ class Profile(ctypes.Structure):
     _fields_ = [("ms", ctypes.c_double * len(K_CLASSES)), ("launches", ctypes.c_int64 * len(K_CLASSES))]
 
 
+AOV_NAMES = ("position", "normal", "albedo")   # PNRT_AOV_* order
+AOV_POSITION, AOV_NORMAL, AOV_ALBEDO = range(3)
+AOV_COUNT = len(AOV_NAMES)
+
+
+class DenoiseParams(ctypes.Structure):
+    """``pnrt_denoise_params``."""
+    _fields_ = [("levels", ctypes.c_int), ("sigma_color", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_position", ctypes.c_float)]
+
+
 def _sig(lib, name, res, *args):
     fn = getattr(lib, name)
     fn.restype = res
@@ -154,6 +165,12 @@ def _type_device(lib):
     _sig(lib, "pnrt_read_env_table", INT, P, F)
     _sig(lib, "pnrt_profile_read", INT, P, ctypes.POINTER(Profile))
     _sig(lib, "pnrt_bvh_build", INT, P, F, INT, F, INT, PINT, I32, PINT)
+    _sig(lib, "pnrt_render_guides", INT, P)
+    _sig(lib, "pnrt_read_aov", INT, P, INT, F)
+    _sig(lib, "pnrt_aov_device_ptr", P, P, INT)
+    _sig(lib, "pnrt_denoise", INT, P, ctypes.POINTER(DenoiseParams))
+    _sig(lib, "pnrt_read_denoised", INT, P, F)
+    _sig(lib, "pnrt_denoised_device_ptr", P, P)
 
 
 def fptr(a) -> ctypes.POINTER(ctypes.c_float):

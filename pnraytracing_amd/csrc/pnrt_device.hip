@@ -21,6 +21,7 @@
 #include "pt_wf.h"
 #include "pt_env.h"
 #include "pt_bvh.h"
+#include "pt_denoise.h"
 
 __global__ void pt_pack_rows_kernel(const float4* accum, float4* dst, int width, int rows, int band,
                                     int n_shards, int shard) {
@@ -163,6 +164,23 @@ struct pnrt_ctx {
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev_pending;
     double prof_ms[PNRT_K_COUNT] = {};
     int64_t prof_n[PNRT_K_COUNT] = {};
+    // guide images and the denoised preview (pnrt_render_guides / pnrt_denoise): every
+    // buffer is allocated on first use, so a context that never asks holds none
+    struct GuideKey {       // what the guide images were rendered for
+        uint64_t epoch = 0, tex_epoch = 0;
+        float cam[12] = {};
+        int width = 0, height = 0, mode = -1;
+        bool valid = false;
+    };
+    uint64_t tex_epoch = 1;                // bumped by pnrt_upload_texture (the albedo image reads the textures)
+    float4* aov[PNRT_AOV_COUNT] = {};      size_t aov_cap[PNRT_AOV_COUNT] = {};
+    GuideKey guide_key;
+    float4* g_primary = nullptr;           size_t g_primary_cap = 0;   // records of the guides' own trace, when no
+    PrimKey g_prim;                                                    // pipe holds the full image's
+    uint2* g_ovf = nullptr;                size_t g_ovf_cap = 0;       // ... and its stack spill area
+    float4* dn_guide = nullptr;            size_t dn_guide_cap = 0;    // compact guide records (pt_denoise.h)
+    float4* dn_img[2] = {};                size_t dn_img_cap[2] = {};  // [0] the denoised image, [1] its ping-pong partner
+    int dn_width = 0, dn_height = 0;       // size of the denoised image (0: none yet)
 };
 
 static int set_err(pnrt_ctx* c, int code, const std::string& m) {
@@ -565,6 +583,63 @@ static int pipes_init(pnrt_ctx* c) {
     return PNRT_OK;
 }
 
+// The trace grid at full occupancy (and that of the lone calls' instantiation), asked once.
+static int trace_grid_init(pnrt_ctx* c) {
+    if (c->trace_grid == 0) {
+        int per_cu = 0, cus = 0;
+        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_wf_trace<WF_STACK, false>, WF_TRACE_BLOCK, 0));
+        HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        c->trace_grid = (per_cu > 0 ? per_cu : 1) * cus;
+        int per_cu_cc = 0;
+        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_cc, pt_wf_trace<WF_STACK, false, true>, WF_TRACE_BLOCK, 0));
+        c->trace_grid_cc = std::min(c->trace_grid, (per_cu_cc > 0 ? per_cu_cc : 1) * cus);
+    }
+    return PNRT_OK;
+}
+
+// The primary records (camera ray's closest hit per pixel of the shard) depend
+// on the camera, the frame size, the shard, the traversal mode and the scene
+// (scene_epoch: arrays, materials, environment) -- not on the frame number: the
+// camera ray has no jitter (ray_tracing.comp:205-211, 980).  Records that were
+// traced for the same key are reused (read-only since), exactly.
+static pnrt_ctx::PrimKey prim_key(const pnrt_ctx* c, const FrameParams& fp) {
+    pnrt_ctx::PrimKey key;
+    key.epoch = c->scene_epoch;
+    std::memcpy(key.cam, fp.eye, 12); std::memcpy(key.cam + 3, fp.llc, 12);
+    std::memcpy(key.cam + 6, fp.hor, 12); std::memcpy(key.cam + 9, fp.ver, 12);
+    key.width = fp.width; key.height = fp.height; key.rows = fp.rows;
+    key.band = fp.band; key.n_shards = fp.n_shards; key.shard = fp.shard; key.mode = fp.mode;
+    key.valid = true;
+    return key;
+}
+// Ensure `primary` holds the records of fp's shard (render_wavefront's pipes and
+// pnrt_render_guides): traced on stream w -- the trace kernel's step, grid-stride,
+// with the spill area `ovf` -- unless `have` says they are there already.  One
+// launch of class PNRT_K_PRIMARY, or none.
+static int ensure_primary(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, hipStream_t w, uint2* ovf, int ovf_stride,
+                          float4* primary, pnrt_ctx::PrimKey& have) {
+    const pnrt_ctx::PrimKey key = prim_key(c, fp);
+    const bool prim_hit = have.valid && have.epoch == key.epoch && !std::memcmp(have.cam, key.cam, sizeof key.cam) &&
+                          have.width == key.width && have.height == key.height && have.rows == key.rows &&
+                          have.band == key.band && have.n_shards == key.n_shards && have.shard == key.shard &&
+                          have.mode == key.mode;
+    if (!prim_hit) {
+        ProfScope ps(c, PNRT_K_PRIMARY, w);
+        const size_t pix = (size_t)fp.rows * fp.width;
+        WfBufs pb{};
+        pb.ovf = ovf;
+        pb.fault = c->fault_dev;
+        pb.ovf_stride = (uint32_t)ovf_stride;
+        const unsigned gp = (unsigned)std::min<size_t>((pix + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
+        if (s.has_leaf_table)
+            hipLaunchKernelGGL((pt_primary_wf<WF_STACK, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, pb, primary);
+        else hipLaunchKernelGGL((pt_primary_wf<WF_STACK, false>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, pb, primary);
+        HIPCHK(c, hipGetLastError());
+        have = key;
+    }
+    return PNRT_OK;
+}
+
 // v3 wavefront, one pnrt_render call on a pipe: the primary pass (unless the
 // pipe's records are still valid, PrimKey), then per group of <= WF_MAX_CHUNK_FRAMES frames one
 // batch (gen -> {trace -> shade} x depth) on the pipe's worker stream, then the
@@ -609,15 +684,7 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
     c->next_pipe = (pi + 1) % npipes;
     c->last_pipe = pi;
     pnrt_ctx::Pipe& P = c->pipe[pi];
-    if (c->trace_grid == 0) {
-        int per_cu = 0, cus = 0;
-        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pt_wf_trace<WF_STACK, false>, WF_TRACE_BLOCK, 0));
-        HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        c->trace_grid = (per_cu > 0 ? per_cu : 1) * cus;
-        int per_cu_cc = 0;
-        HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_cc, pt_wf_trace<WF_STACK, false, true>, WF_TRACE_BLOCK, 0));
-        c->trace_grid_cc = std::min(c->trace_grid, (per_cu_cc > 0 ? per_cu_cc : 1) * cus);
-    }
+    if ((rc = trace_grid_init(c))) return rc;
     // per-lane spill area of the trace kernel's stack: LDS holds WF_STACK entries
     const int ovf_stride = c->wf_stack_need > WF_STACK ? c->wf_stack_need - WF_STACK : 1;
     const size_t ovf_bytes = (size_t)c->trace_grid * WF_TRACE_BLOCK * ovf_stride * 8;
@@ -646,36 +713,8 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
     if (stagger && !alone && prev_pipe != pi && prev_pipe < WF_PIPES && c->pipe[prev_pipe].stage_set)
         HIPCHK(c, hipStreamWaitEvent(w, c->pipe[prev_pipe].ev_stage, 0));
     P.stage_set = false;
-    // The primary records (camera ray's closest hit per pixel of the shard) depend
-    // on the camera, the frame size, the shard, the traversal mode and the scene
-    // (scene_epoch: arrays, materials, environment) -- not on the frame number: the
-    // camera ray has no jitter (ray_tracing.comp:205-211, 980).  A pipe whose
-    // records were traced for the same key reuses them (read-only since), exactly.
-    pnrt_ctx::PrimKey key;
-    key.epoch = c->scene_epoch;
-    std::memcpy(key.cam, fp.eye, 12); std::memcpy(key.cam + 3, fp.llc, 12);
-    std::memcpy(key.cam + 6, fp.hor, 12); std::memcpy(key.cam + 9, fp.ver, 12);
-    key.width = fp.width; key.height = fp.height; key.rows = fp.rows;
-    key.band = fp.band; key.n_shards = fp.n_shards; key.shard = fp.shard; key.mode = fp.mode;
-    key.valid = true;
-    const bool prim_hit = P.prim.valid && P.prim.epoch == key.epoch && !std::memcmp(P.prim.cam, key.cam, sizeof key.cam) &&
-                          P.prim.width == key.width && P.prim.height == key.height && P.prim.rows == key.rows &&
-                          P.prim.band == key.band && P.prim.n_shards == key.n_shards && P.prim.shard == key.shard &&
-                          P.prim.mode == key.mode;
-    if (!prim_hit) {
-        ProfScope ps(c, PNRT_K_PRIMARY, w);
-        // the trace kernel's step, grid-stride, the pipe's spill area
-        WfBufs pb{};
-        pb.ovf = P.ovf;
-        pb.fault = c->fault_dev;
-        pb.ovf_stride = (uint32_t)ovf_stride;
-        const unsigned gp = (unsigned)std::min<size_t>((pix + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
-        if (s.has_leaf_table)
-            hipLaunchKernelGGL((pt_primary_wf<WF_STACK, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, pb, P.primary);
-        else hipLaunchKernelGGL((pt_primary_wf<WF_STACK, false>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, pb, P.primary);
-        HIPCHK(c, hipGetLastError());
-        P.prim = key;
-    }
+    // the pipe's primary records: traced now, or still valid from an earlier call (PrimKey)
+    if ((rc = ensure_primary(c, s, fp, w, P.ovf, ovf_stride, P.primary, P.prim))) return rc;
     for (uint32_t f0 = 0; f0 < nf; f0 += chunk) {
         const uint32_t cf = (nf - f0) < chunk ? (nf - f0) : chunk;
         WfLayout a = wf_layout(static_cast<char*>(P.wf), per_frame * cf);
@@ -708,6 +747,143 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
 }
 
 static void free_env(pnrt_ctx* c);
+
+// The scene as the kernels take it: the uploaded arrays with the environment,
+// the textures and the fault words bound now.
+static DevScene launch_scene(const pnrt_ctx* c) {
+    DevScene s = c->scene;
+    s.hdr = static_cast<const float4*>(c->hdr);
+    s.rnd = static_cast<const float4*>(c->rnd);
+    s.hdr_q = static_cast<const float4*>(c->hdr_q);
+    s.rnd_q = static_cast<const float4*>(c->rnd_q);
+    s.n_tex = PT_MAX_TEXTURES;
+    for (int i = 0; i < PT_MAX_TEXTURES; ++i) {
+        s.tex[i] = static_cast<const uint32_t*>(c->tex[i]);
+        s.tex_w[i] = c->tex_w[i]; s.tex_h[i] = c->tex_h[i];
+    }
+    s.unorm8 = c->unorm8;
+    s.fault = c->fault_dev;
+    s.diag_force = 0;
+    return s;
+}
+
+// ---- guide images and the denoised preview -------------------------------------------------
+// The camera and effective traversal mode of the current frame, as FrameParams
+// of the whole image (one band, one shard).
+static FrameParams full_frame_params(const pnrt_ctx* c) {
+    FrameParams fp;
+    std::memcpy(fp.eye, c->cam.eye, 12); std::memcpy(fp.llc, c->cam.lower_left, 12);
+    std::memcpy(fp.hor, c->cam.horizontal, 12); std::memcpy(fp.ver, c->cam.vertical, 12);
+    fp.width = c->width; fp.height = c->height; fp.max_depth = c->max_bounce;
+    fp.first_frame = 0; fp.n_frames = 1;
+    fp.band = 1; fp.n_shards = 1; fp.shard = 0;
+    fp.rows = c->height;
+    fp.mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
+    return fp;
+}
+// What guide images rendered now would be rendered for (pnrt_denoise compares).
+static pnrt_ctx::GuideKey guide_key_now(const pnrt_ctx* c) {
+    pnrt_ctx::GuideKey k;
+    k.epoch = c->scene_epoch;
+    k.tex_epoch = c->tex_epoch;
+    std::memcpy(k.cam, c->cam.eye, 12); std::memcpy(k.cam + 3, c->cam.lower_left, 12);
+    std::memcpy(k.cam + 6, c->cam.horizontal, 12); std::memcpy(k.cam + 9, c->cam.vertical, 12);
+    k.width = c->width; k.height = c->height;
+    k.mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
+    k.valid = true;
+    return k;
+}
+static bool guide_key_eq(const pnrt_ctx::GuideKey& a, const pnrt_ctx::GuideKey& b) {
+    return a.valid && b.valid && a.epoch == b.epoch && a.tex_epoch == b.tex_epoch && !std::memcmp(a.cam, b.cam, sizeof a.cam) &&
+           a.width == b.width && a.height == b.height && a.mode == b.mode;
+}
+
+static int render_guides(pnrt_ctx* c) {
+    int rc;
+    if ((rc = pipes_init(c)) || (rc = trace_grid_init(c))) return rc;
+    const DevScene s = launch_scene(c);
+    const FrameParams fp = full_frame_params(c);
+    const size_t pix = (size_t)c->width * c->height;
+    if (pix > 0xFFFFFFFFull / 64) return set_err(c, PNRT_E_ARG, "render_guides: frame too large");
+    for (int k = 0; k < PNRT_AOV_COUNT; ++k)
+        if ((rc = grow(c, (void**)&c->aov[k], &c->aov_cap[k], pix * 16))) return rc;
+    // A pipe that holds the records of the whole image (any band: one shard owns
+    // every row, in row order) for this camera, scene and mode lends them, read-only.
+    // Its worker wrote them before the call's blend, which the context stream has
+    // waited for; the pipe's next call waits for ev_blend before it may retrace
+    // them, so the event is recorded again behind the kernel that reads them here.
+    pnrt_ctx::PrimKey want = prim_key(c, fp);
+    pnrt_ctx::Pipe* lender = nullptr;
+    for (auto& Q : c->pipe) {
+        const pnrt_ctx::PrimKey& h = Q.prim;
+        if (Q.primary && Q.blend_pending && h.valid && h.epoch == want.epoch && !std::memcmp(h.cam, want.cam, sizeof want.cam) &&
+            h.width == want.width && h.height == want.height && h.rows == want.rows && h.n_shards == 1 && h.shard == 0 &&
+            h.mode == want.mode) {
+            lender = &Q;
+            break;
+        }
+    }
+    const float4* rec = nullptr;
+    if (lender) {
+        rec = lender->primary;
+    } else {            // records of the guides' own, in a buffer and a spill area no pipe uses
+        const int ovf_stride = c->wf_stack_need > WF_STACK ? c->wf_stack_need - WF_STACK : 1;
+        const size_t ovf_bytes = (size_t)c->trace_grid * WF_TRACE_BLOCK * ovf_stride * 8;
+        const float4* old = c->g_primary;
+        if ((rc = grow(c, (void**)&c->g_primary, &c->g_primary_cap, pix * 48)) ||
+            (rc = grow(c, (void**)&c->g_ovf, &c->g_ovf_cap, ovf_bytes)))
+            return rc;
+        if (c->g_primary != old) c->g_prim.valid = false;
+        if ((rc = ensure_primary(c, s, fp, c->stream, c->g_ovf, ovf_stride, c->g_primary, c->g_prim))) return rc;
+        rec = c->g_primary;
+    }
+    hipLaunchKernelGGL(pt_guides, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, s, rec,
+                       c->aov[PNRT_AOV_POSITION], c->aov[PNRT_AOV_NORMAL], c->aov[PNRT_AOV_ALBEDO], (uint32_t)pix);
+    HIPCHK(c, hipGetLastError());
+    if (lender) HIPCHK(c, hipEventRecord(lender->ev_blend, c->stream));
+    c->guide_key = guide_key_now(c);
+    return mark_stream(c);
+}
+
+static int denoise(pnrt_ctx* c, const pnrt_denoise_params& p) {
+    int rc;
+    const size_t pix = (size_t)c->width * c->height;
+    if ((rc = grow(c, (void**)&c->dn_guide, &c->dn_guide_cap, pix * 32)) ||
+        (rc = grow(c, (void**)&c->dn_img[0], &c->dn_img_cap[0], pix * 16)) ||
+        (rc = grow(c, (void**)&c->dn_img[1], &c->dn_img_cap[1], pix * 16)))
+        return rc;
+    DenoiseParams d{};
+    d.width = c->width; d.height = c->height;
+    const dim3 grid((unsigned)((c->width + 15) / 16), (unsigned)((c->height + 15) / 16));
+    // level i reads image (first + i) & 1 and writes the other, so the last one writes dn_img[0]
+    const int first = p.levels & 1;
+    hipLaunchKernelGGL(pt_denoise_prep, grid, dim3(256), 0, c->stream, d, c->scene.materials, c->scene.n_materials,
+                       (const float4*)c->accum, (const float4*)c->aov[PNRT_AOV_POSITION], (const float4*)c->aov[PNRT_AOV_NORMAL],
+                       (const float4*)c->aov[PNRT_AOV_ALBEDO], c->dn_guide, c->dn_img[first]);
+    HIPCHK(c, hipGetLastError());
+    d.inv_n = 1.0f / (p.sigma_normal * p.sigma_normal);
+    d.inv_p = 1.0f / (p.sigma_position * p.sigma_position);
+    for (int i = 0; i < p.levels; ++i) {
+        const float sc = p.sigma_color * std::ldexp(1.0f, -i);
+        d.inv_c = 1.0f / (sc * sc);
+        d.step = 1 << i;
+        const float4* src = c->dn_img[(first + i) & 1];
+        float4* dst = c->dn_img[(first + i + 1) & 1];
+        // spacings 1, 2, 4 through an LDS tile with halo, 8 and 16 through the caches (pt_denoise.h)
+        const bool last = i + 1 == p.levels;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, d, (const float4*)c->dn_guide, src, dst,
+                               (const float4*)c->accum, (const float4*)c->aov[PNRT_AOV_ALBEDO]);
+        };
+        if (d.step == 1 && DN_LDS_MAX_STEP >= 1) last ? launch(pt_denoise_pass_lds<1, true>) : launch(pt_denoise_pass_lds<1, false>);
+        else if (d.step == 2 && DN_LDS_MAX_STEP >= 2) last ? launch(pt_denoise_pass_lds<2, true>) : launch(pt_denoise_pass_lds<2, false>);
+        else if (d.step == 4 && DN_LDS_MAX_STEP >= 4) last ? launch(pt_denoise_pass_lds<4, true>) : launch(pt_denoise_pass_lds<4, false>);
+        else last ? launch(pt_denoise_pass<true>) : launch(pt_denoise_pass<false>);
+        HIPCHK(c, hipGetLastError());
+    }
+    c->dn_width = c->width; c->dn_height = c->height;
+    return mark_stream(c);
+}
 
 extern "C" {
 
@@ -794,6 +970,9 @@ void pnrt_destroy(pnrt_ctx* c) {
         if (P.ev_blend) (void)hipEventDestroy(P.ev_blend);
         if (P.ev_stage) (void)hipEventDestroy(P.ev_stage);
     }
+    for (float4* a : c->aov) (void)hipFree(a);
+    (void)hipFree(c->g_primary); (void)hipFree(c->g_ovf); (void)hipFree(c->dn_guide);
+    (void)hipFree(c->dn_img[0]); (void)hipFree(c->dn_img[1]);
 
     for (auto& p : c->ev_pending) { c->ev_pool.push_back(p.second.first); c->ev_pool.push_back(p.second.second); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1131,6 +1310,7 @@ int pnrt_upload_texture(pnrt_ctx* c, int slot, const uint8_t* px, int w, int h, 
     HIPCHK(c, hipMalloc(&c->tex[slot], texels.size() * 4));
     HIPCHK(c, hipMemcpy(c->tex[slot], texels.data(), texels.size() * 4, hipMemcpyHostToDevice));
     c->tex_w[slot] = w; c->tex_h[slot] = h;
+    ++c->tex_epoch;                      // the albedo guide image samples the textures
     return PNRT_OK;
 }
 
@@ -1294,19 +1474,7 @@ int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int
     fp.rows = shard_rows(c->height, band, nsh, shard);
     fp.mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
     if (fp.rows == 0) return PNRT_OK;
-    DevScene s = c->scene;
-    s.hdr = static_cast<const float4*>(c->hdr);
-    s.rnd = static_cast<const float4*>(c->rnd);
-    s.hdr_q = static_cast<const float4*>(c->hdr_q);
-    s.rnd_q = static_cast<const float4*>(c->rnd_q);
-    s.n_tex = PT_MAX_TEXTURES;
-    for (int i = 0; i < PT_MAX_TEXTURES; ++i) {
-        s.tex[i] = static_cast<const uint32_t*>(c->tex[i]);
-        s.tex_w[i] = c->tex_w[i]; s.tex_h[i] = c->tex_h[i];
-    }
-    s.unorm8 = c->unorm8;
-    s.fault = c->fault_dev;
-    s.diag_force = 0;
+    DevScene s = launch_scene(c);
     if (WF_DIAG_BOUNDS) {                // the bounds check's own test (diagnostic builds only)
         const char* f = getenv("PNRT_DIAG_FORCE_OOB");
         s.diag_force = (f && atoi(f) > 0) ? 1 : 0;
@@ -1372,6 +1540,61 @@ int pnrt_read_accum(pnrt_ctx* c, float* out) {
 }
 
 void* pnrt_accum_device_ptr(pnrt_ctx* c) { return c ? c->accum : nullptr; }
+
+int pnrt_render_guides(pnrt_ctx* c) {
+    if (!c) return PNRT_E_ARG;
+    if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, "render_guides: upload_scene and set_frame first");
+    if (int rc = check_fault(c)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return render_guides(c);
+}
+
+int pnrt_read_aov(pnrt_ctx* c, int which, float* out) {
+    if (!c || !out) return PNRT_E_ARG;
+    if (which < 0 || which >= PNRT_AOV_COUNT) return set_err(c, PNRT_E_ARG, "read_aov: unknown guide image");
+    if (!c->guide_key.valid || !c->aov[which]) return set_err(c, PNRT_E_STATE, "read_aov: render_guides first");
+    if (c->guide_key.width != c->width || c->guide_key.height != c->height)
+        return set_err(c, PNRT_E_STATE, "read_aov: the guide images have another size than the frame: render_guides again");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->aov[which], (size_t)c->guide_key.width * c->guide_key.height * 16, hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, sync_all(c));
+    return check_fault(c);
+}
+
+void* pnrt_aov_device_ptr(pnrt_ctx* c, int which) {
+    return (c && which >= 0 && which < PNRT_AOV_COUNT) ? c->aov[which] : nullptr;
+}
+
+int pnrt_denoise(pnrt_ctx* c, const pnrt_denoise_params* params) {
+    if (!c) return PNRT_E_ARG;
+    pnrt_denoise_params p = {5, 2.0f, 0.25f, 0.5f};      // the defaults (pnrt.h)
+    if (params) p = *params;
+    if (p.levels < 1 || p.levels > 5) return set_err(c, PNRT_E_ARG, "denoise: levels must be 1..5");
+    for (float sg : {p.sigma_color, p.sigma_normal, p.sigma_position})
+        if (!std::isfinite(sg) || !(sg > 0.0f)) return set_err(c, PNRT_E_ARG, "denoise: every sigma must be finite and > 0");
+    if (!c->has_scene || !c->has_frame || !c->accum) return set_err(c, PNRT_E_STATE, "denoise: upload_scene and set_frame first");
+    if (!c->guide_key.valid) return set_err(c, PNRT_E_STATE, "denoise: render_guides first");
+    if (!guide_key_eq(c->guide_key, guide_key_now(c)))
+        return set_err(c, PNRT_E_STATE, "denoise: the guide images are stale (camera, size, scene, materials, textures, "
+                                        "environment or traversal mode changed): render_guides again");
+    if (int rc = check_fault(c)) return rc;      // completed work that faulted
+    HIPCHK(c, hipSetDevice(c->device));
+    return denoise(c, p);
+}
+
+int pnrt_read_denoised(pnrt_ctx* c, float* out) {
+    if (!c || !out) return PNRT_E_ARG;
+    if (!c->dn_width || !c->dn_img[0]) return set_err(c, PNRT_E_STATE, "read_denoised: denoise first");
+    if (c->dn_width != c->width || c->dn_height != c->height)
+        return set_err(c, PNRT_E_STATE, "read_denoised: the denoised image has another size than the frame: denoise again");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->dn_img[0], (size_t)c->width * c->height * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, sync_all(c));
+    return check_fault(c);
+}
+
+void* pnrt_denoised_device_ptr(pnrt_ctx* c) { return c ? c->dn_img[0] : nullptr; }
 
 int pnrt_profile_enable(pnrt_ctx* c, int on) {
     if (!c) return PNRT_E_ARG;

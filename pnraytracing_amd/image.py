@@ -50,16 +50,33 @@ def _attr(name: str, typ: str, data: bytes) -> bytes:
     return name.encode() + b"\0" + typ.encode() + b"\0" + struct.pack("<i", len(data)) + data
 
 
-def write_exr(path: str, accum: np.ndarray) -> None:
+def write_exr(path: str, accum: np.ndarray, layers: dict | None = None) -> None:
     """OpenEXR 2.0, single-part scanline image, no compression, 32-bit float
     R, G, B, A (the accumulation image as stored, lossless), top row first.
     Written from the format's published layout (magic, version, attribute
-    header, scanline offset table, one scanline per chunk); no library needed."""
+    header, scanline offset table, one scanline per chunk); no library needed.
+    ``layers``: name -> (H, W, C) image of the same size (C = 3 or 4: the guide
+    images, the denoised preview), written as further float channels
+    ``name.R``, ``name.G``, ``name.B`` [, ``name.A``] (read_exr_layers)."""
     a = np.asarray(accum, np.float32)
     h, w = a.shape[:2]
     ch = a.shape[2] if a.ndim == 3 else 1
     names = ["R", "G", "B", "A"][:ch] if ch in (3, 4) else ["Y"]
-    order = sorted(range(len(names)), key=lambda k: names[k])    # channels are stored in name order
+    top = a[::-1].reshape(h, w, len(names))                     # GL row 0 is the bottom
+    planes = [top[:, :, k] for k in range(len(names))]
+    for lname, img in (layers or {}).items():
+        li = np.asarray(img, np.float32)
+        if li.ndim != 3 or li.shape[:2] != (h, w) or li.shape[2] not in (3, 4):
+            raise ValueError(f"layer {lname!r}: need a ({h}, {w}, 3 or 4) image, got {li.shape}")
+        if not lname or "." in lname or "\0" in lname or len(lname.encode()) > 29:
+            # (a channel name of a file without the long-names flag has at most 31 bytes)
+            raise ValueError(f"layer name {lname!r}: must be non-empty, without '.' and at most 29 bytes")
+        for k in range(li.shape[2]):
+            names.append(f"{lname}.{'RGBA'[k]}")
+            planes.append(li[::-1, :, k])
+    if len(set(names)) != len(names):
+        raise ValueError("duplicate channel names")
+    order = sorted(range(len(names)), key=lambda k: names[k].encode())   # channels are stored in name order
     chlist = b"".join(names[k].encode() + b"\0" + struct.pack("<iB3xii", 2, 0, 1, 1) for k in order) + b"\0"
     box = struct.pack("<4i", 0, 0, w - 1, h - 1)
     header = (b"\x76\x2f\x31\x01" + struct.pack("<i", 2) +
@@ -68,7 +85,6 @@ def write_exr(path: str, accum: np.ndarray) -> None:
               _attr("lineOrder", "lineOrder", b"\0") + _attr("pixelAspectRatio", "float", struct.pack("<f", 1.0)) +
               _attr("screenWindowCenter", "v2f", struct.pack("<2f", 0.0, 0.0)) +
               _attr("screenWindowWidth", "float", struct.pack("<f", 1.0)) + b"\0")
-    top = a[::-1].reshape(h, w, len(names))                     # GL row 0 is the bottom
     line_bytes = w * 4 * len(names)
     first = len(header) + 8 * h
     offsets = struct.pack(f"<{h}Q", *(first + y * (8 + line_bytes) for y in range(h)))
@@ -78,12 +94,12 @@ def write_exr(path: str, accum: np.ndarray) -> None:
         for y in range(h):
             f.write(struct.pack("<ii", y, line_bytes))
             for k in order:
-                f.write(np.ascontiguousarray(top[y, :, k], "<f4").tobytes())
+                f.write(np.ascontiguousarray(planes[k][y], "<f4").tobytes())
 
 
-def read_exr(path: str) -> np.ndarray:
-    """The images write_exr writes (uncompressed scanline float): (H, W, C) float32,
-    row 0 = bottom, channels R, G, B[, A]."""
+def _read_exr_channels(path: str):
+    """Channel names (file order) and the (H, W, n) float32 image, top row first, of
+    an uncompressed 32-bit-float scanline file."""
     b = open(path, "rb").read()
     if b[:4] != b"\x76\x2f\x31\x01":
         raise ValueError("not an OpenEXR file")
@@ -112,5 +128,23 @@ def read_exr(path: str) -> np.ndarray:
         y, size = struct.unpack_from("<ii", b, o)
         line = np.frombuffer(b, "<f4", size // 4, o + 8).reshape(len(names), w)
         img[y - y0] = line.T
+    return names, img
+
+
+def read_exr(path: str) -> np.ndarray:
+    """The images write_exr writes (uncompressed scanline float): (H, W, C) float32,
+    row 0 = bottom, channels R, G, B[, A] (layers, if any, are left out: read_exr_layers)."""
+    names, img = _read_exr_channels(path)
     want = [c for c in ("R", "G", "B", "A", "Y") if c in names]
     return img[::-1][:, :, [names.index(c) for c in want]]
+
+
+def read_exr_layers(path: str) -> dict:
+    """The layers write_exr(..., layers=...) wrote: name -> (H, W, C) float32, row 0 =
+    bottom, channels R, G, B[, A]."""
+    names, img = _read_exr_channels(path)
+    out = {}
+    for lname in sorted({n.rsplit(".", 1)[0] for n in names if "." in n}):
+        want = [f"{lname}.{c}" for c in "RGBA" if f"{lname}.{c}" in names]
+        out[lname] = np.ascontiguousarray(img[::-1][:, :, [names.index(c) for c in want]])
+    return out

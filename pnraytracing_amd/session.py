@@ -95,3 +95,18 @@ class InteractiveSession:
         if not redraw:                               # main.cpp:628
             self.frame_count += 1
         return depth, self.frame_count
+
+    def preview(self, **params):
+        """The denoised preview of the accumulation image as it stands (after ``frame()``,
+        before the display: main.cpp:613 / :618-628).  The guide images are rendered only
+        when the camera or the scene changed since the last call -- the library says so
+        (PNRT_E_STATE from pnrt_denoise) -- then the image is filtered.  ``params`` are
+        ``PathTracer.denoise``'s; read the result with ``PathTracer.read_denoised()``."""
+        from .tracer import PnrtError
+        try:
+            self.pt.denoise(**params)
+        except PnrtError as e:
+            if getattr(e, "code", 0) != -3:          # PNRT_E_STATE: no guides yet, or stale ones
+                raise
+            self.pt.render_guides()
+            self.pt.denoise(**params)

@@ -19,6 +19,8 @@ TRAVERSE_EXACT = 0
 TRAVERSE_ZCULL = 1
 KERNEL_V1 = 0x100      # | with a traverse mode: one-lane-per-pixel A/B baseline kernel
 SERIAL = 0x200         # | measurement: one call in flight, full trace grid (exclusive kernel times)
+# pnrt_denoise(ctx, NULL)'s parameters (include/pnrt.h)
+DENOISE_DEFAULTS = {"levels": 5, "sigma_color": 2.0, "sigma_normal": 0.25, "sigma_position": 0.5}
 
 
 class PnrtError(RuntimeError):
@@ -53,7 +55,9 @@ class PathTracer:
 
     def _ck(self, rc, what):
         if rc != 0:
-            raise PnrtError(f"{what} failed ({rc}): {self._lib.pnrt_last_error(self._ctx).decode()}")
+            e = PnrtError(f"{what} failed ({rc}): {self._lib.pnrt_last_error(self._ctx).decode()}")
+            e.code = rc                  # the PNRT_E_* code
+            raise e
 
     # ---- uploads ---------------------------------------------------------------------
     def upload_scene(self, p: PackedScene):
@@ -166,6 +170,51 @@ class PathTracer:
 
     def accum_ptr(self) -> int:
         return int(self._lib.pnrt_accum_device_ptr(self._ctx) or 0)
+
+    # ---- guide images and the denoised preview -------------------------------------------
+    @staticmethod
+    def _aov(name) -> int:
+        if isinstance(name, str):
+            if name not in N.AOV_NAMES:
+                raise ValueError(f"unknown guide image {name!r}: one of {N.AOV_NAMES}")
+            return N.AOV_NAMES.index(name)
+        return int(name)
+
+    def render_guides(self):
+        """First-hit position / normal / albedo images of the whole frame for the current
+        camera, scene and traversal mode (pnrt_render_guides); asynchronous."""
+        self._ck(self._lib.pnrt_render_guides(self._ctx), "pnrt_render_guides")
+
+    def read_aov(self, name) -> np.ndarray:
+        """One guide image, (H, W, 4) float32, row 0 = bottom: ``"position"`` (w = hit flag),
+        ``"normal"`` (w = material id, -1 on a miss) or ``"albedo"`` (w = texture id or -1)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self._lib.pnrt_read_aov(self._ctx, self._aov(name), N.fptr(out)), "pnrt_read_aov")
+        return out
+
+    def aov_ptr(self, name) -> int:
+        return int(self._lib.pnrt_aov_device_ptr(self._ctx, self._aov(name)) or 0)
+
+    def denoise(self, levels: int | None = None, sigma_color: float | None = None, sigma_normal: float | None = None,
+                sigma_position: float | None = None):
+        """The a-trous preview of the accumulation image into the denoised image
+        (pnrt_denoise); asynchronous.  Arguments left out take the library's defaults."""
+        given = (levels, sigma_color, sigma_normal, sigma_position)
+        if all(v is None for v in given):
+            params = None
+        else:
+            d = DENOISE_DEFAULTS
+            p = N.DenoiseParams(*(d[k] if v is None else v for k, v in zip(d, given)))
+            params = ctypes.byref(p)
+        self._ck(self._lib.pnrt_denoise(self._ctx, params), "pnrt_denoise")
+
+    def read_denoised(self) -> np.ndarray:
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self._lib.pnrt_read_denoised(self._ctx, N.fptr(out)), "pnrt_read_denoised")
+        return out
+
+    def denoised_ptr(self) -> int:
+        return int(self._lib.pnrt_denoised_device_ptr(self._ctx) or 0)
 
     def pack_rows(self, dst_ptr: int, band: int, n_shards: int, shard: int):
         self._ck(self._lib.pnrt_pack_rows(self._ctx, ctypes.c_void_p(dst_ptr), band, n_shards, shard), "pnrt_pack_rows")
