@@ -253,6 +253,62 @@ int pnrt_read_denoised(pnrt_ctx* ctx, float* rgba_out);
  * same pointer after every call at one frame size). */
 void* pnrt_denoised_device_ptr(pnrt_ctx* ctx);
 
+/* Per-pixel sample moments and a convergence measure (not in the reference, which
+ * counts frames: main.cpp:628).  Opt-in: while enabled, the blend of every
+ * pnrt_render batch also folds the batch's per-frame colours into a moments image,
+ * one 16-byte record per pixel, width*height records, row 0 = bottom:
+ *   x = running mean of the luminance    y = M2, the sum of squared deviations
+ *   z = 0 (reserved)                     w = n, the frames folded in, as uint32 bits
+ * For each frame, in frame order, with the frame's colour c:
+ *   Y = ((0.2126f * c.x) + (0.7152f * c.y)) + (0.0722f * c.z)
+ *   frame number 0: n = 0, mean = 0, M2 = 0 first (frame 0 overwrites the accumulation)
+ *   n = n + 1 (saturating);  d = Y - mean;  mean = mean + d * (1.0f / (float)n);
+ *   M2 = M2 + d * (Y - mean)
+ * The accumulation image, the launch count and the profile classes are the same with
+ * and without (the blend-with-moments kernel is timed as PNRT_K_BLEND); a context
+ * that never enables them launches what it always did.
+ *
+ * on = 1 / 0 (anything else PNRT_E_ARG).  Waits for the calls in flight.  The first
+ * enable allocates the image, zeroed (with the frame, when pnrt_set_frame comes
+ * later); enabling again keeps the data; disabling stops the updates and keeps the
+ * image.  From the first enable on, pnrt_reset_accum zeroes the moments and a size
+ * change in pnrt_set_frame reallocates them zeroed.  While enabled, pnrt_render under
+ * PNRT_KERNEL_V1 returns PNRT_E_STATE and queues nothing (the one-kernel path has no
+ * per-frame colours). */
+int pnrt_enable_moments(pnrt_ctx* ctx, int on);
+/* Device pointer of the moments image (NULL before the first enable). */
+void* pnrt_moments_device_ptr(pnrt_ctx* ctx);
+/* Synchronise and copy the width*height*4 floats of the moments image (w: uint32
+ * bits) to the host.  PNRT_E_STATE when moments were never enabled. */
+int pnrt_read_moments(pnrt_ctx* ctx, float* rgba_out);
+/* The per-pixel relative standard error of the mean, width*height floats, row 0 =
+ * bottom: for n >= 2
+ *   var = M2 / (float)(n - 1);  sem = sqrtf(var / (float)n);
+ *   e = sem / fmaxf(mean, 1.0f / 256.0f);  e_c = (e <= 65535.0f) ? e : 65535.0f
+ * (IEEE division and square root; the comparison also sends NaN to 65535), and +inf
+ * for an unmeasured pixel (n < 2).  Synchronous.  PNRT_E_STATE as pnrt_read_moments. */
+int pnrt_read_error(pnrt_ctx* ctx, float* out);
+/* Statistics of e_c over the rows of a shard selector (as pnrt_pack_rows takes it).
+ * Every field is an integer or a maximum, combined on the device with integer
+ * atomics, so the result does not depend on the order the blocks finish in.
+ * Statistics of disjoint selectors add up: sum the counts and sum_q16, take the
+ * max of max_error and max_frames and the min of min_frames -- N ranks combine
+ * their own rows' numbers. */
+typedef struct {
+    int64_t  n_pixels;      /* pixels of the selector's rows                         */
+    int64_t  n_measured;    /* ... with n >= 2                                       */
+    int64_t  n_above;       /* measured pixels with e_c > threshold                  */
+    int64_t  sum_q16;       /* sum over measured pixels of (uint32)(e_c * 65536.0f)  */
+    float    max_error;     /* max e_c over measured pixels, 0 when none             */
+    uint32_t min_frames, max_frames;   /* n over all pixels of the rows, 0 when none */
+    uint32_t reserved;      /* 0 */
+} pnrt_convergence_stats;   /* 48 bytes */
+/* Synchronous; a shard without rows gives all zeros.  threshold must be finite and
+ * >= 0 (PNRT_E_ARG otherwise, as a bad selector).  PNRT_E_STATE when moments were
+ * never enabled.  PNRT_E_TRACE as pnrt_read_accum returns it. */
+int pnrt_convergence(pnrt_ctx* ctx, float threshold, int band_rows, int n_shards, int shard,
+                     pnrt_convergence_stats* out);
+
 /* Per-kernel timing (not in the reference, which has no GPU timers): while
  * enabled, every launch of a kernel class is bracketed by HIP events recorded on
  * the launch stream; pnrt_profile_read synchronises and returns the summed

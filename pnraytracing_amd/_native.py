@@ -106,6 +106,13 @@ class DenoiseParams(ctypes.Structure):
                 ("sigma_position", ctypes.c_float)]
 
 
+class ConvergenceStats(ctypes.Structure):
+    """``pnrt_convergence_stats`` (48 bytes)."""
+    _fields_ = [("n_pixels", ctypes.c_int64), ("n_measured", ctypes.c_int64), ("n_above", ctypes.c_int64),
+                ("sum_q16", ctypes.c_int64), ("max_error", ctypes.c_float), ("min_frames", ctypes.c_uint32),
+                ("max_frames", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 def _sig(lib, name, res, *args):
     fn = getattr(lib, name)
     fn.restype = res
@@ -171,6 +178,11 @@ def _type_device(lib):
     _sig(lib, "pnrt_denoise", INT, P, ctypes.POINTER(DenoiseParams))
     _sig(lib, "pnrt_read_denoised", INT, P, F)
     _sig(lib, "pnrt_denoised_device_ptr", P, P)
+    _sig(lib, "pnrt_enable_moments", INT, P, INT)
+    _sig(lib, "pnrt_moments_device_ptr", P, P)
+    _sig(lib, "pnrt_read_moments", INT, P, F)
+    _sig(lib, "pnrt_read_error", INT, P, F)
+    _sig(lib, "pnrt_convergence", INT, P, ctypes.c_float, INT, INT, INT, ctypes.POINTER(ConvergenceStats))
 
 
 def fptr(a) -> ctypes.POINTER(ctypes.c_float):

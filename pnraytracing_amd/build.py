@@ -27,7 +27,7 @@ ARCH = os.environ.get("PNRT_OFFLOAD_ARCH", "gfx950")
 
 DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
-               "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pn_math.h", "sobol_v.inc"]
+               "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pn_math.h", "sobol_v.inc"]
 
 
 def _run(cmd, cwd=None):
@@ -132,6 +132,12 @@ def build_abi_caller(force=False):
     cout = os.path.join(REPO, "tests", "abi", "c_abi_denoise")
     if os.path.exists(csrc) and (force or _stale(cout, deps[1:2] + deps[3:4] + [csrc])):
         _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, csrc, "-o", cout, "-L", PKG, "-lpnrt",
+              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
+    # the sample moments and the convergence statistics from a C translation unit (tests/test_gpu_moments_c_abi.py)
+    vsrc = os.path.join(REPO, "tests", "abi", "c_abi_convergence.c")
+    vout = os.path.join(REPO, "tests", "abi", "c_abi_convergence")
+    if os.path.exists(vsrc) and (force or _stale(vout, deps[1:2] + deps[3:4] + [vsrc])):
+        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, vsrc, "-o", vout, "-L", PKG, "-lpnrt",
               "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
     # the multi-GPU caller: one process, one RCCL communicator per device (ncclCommInitAll + ncclGather)
     msrc = os.path.join(REPO, "tests", "abi", "c_abi_multigpu.cpp")

@@ -22,6 +22,7 @@
 #include "pt_env.h"
 #include "pt_bvh.h"
 #include "pt_denoise.h"
+#include "pt_moments.h"
 
 __global__ void pt_pack_rows_kernel(const float4* accum, float4* dst, int width, int rows, int band,
                                     int n_shards, int shard) {
@@ -181,6 +182,12 @@ struct pnrt_ctx {
     float4* dn_guide = nullptr;            size_t dn_guide_cap = 0;    // compact guide records (pt_denoise.h)
     float4* dn_img[2] = {};                size_t dn_img_cap[2] = {};  // [0] the denoised image, [1] its ping-pong partner
     int dn_width = 0, dn_height = 0;       // size of the denoised image (0: none yet)
+    // per-pixel sample moments (pnrt_enable_moments; pt_moments.h): none until the first enable
+    bool moments_on = false;               // the blends update them
+    bool moments_ever = false;             // enabled at least once: the image follows the frame size from then on
+    float4* moments = nullptr;             // width * height records, as the accumulation image
+    float* mom_err = nullptr;              size_t mom_err_cap = 0;     // pnrt_read_error's image
+    MomentsStats* mom_stats = nullptr;     // pnrt_convergence's device record
 };
 
 static int set_err(pnrt_ctx* c, int code, const std::string& m) {
@@ -735,8 +742,12 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
         }
         {   // the blends run in call order on the caller's stream
             ProfScope ps(c, PNRT_K_BLEND);
-            hipLaunchKernelGGL(pt_blend_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, fp,
-                               (const float4*)P.colors, c->accum, (int)cf, first + f0);
+            if (c->moments_on)          // the same blend, and the moments of the batch's frames (pt_moments.h)
+                hipLaunchKernelGGL(pt_blend_moments_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, fp,
+                                   (const float4*)P.colors, c->accum, c->moments, (int)cf, first + f0);
+            else
+                hipLaunchKernelGGL(pt_blend_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, fp,
+                                   (const float4*)P.colors, c->accum, (int)cf, first + f0);
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(P.ev_blend, c->stream));
@@ -885,6 +896,17 @@ static int denoise(pnrt_ctx* c, const pnrt_denoise_params& p) {
     return mark_stream(c);
 }
 
+// A zeroed moments image of the current frame size, in place of the old one (the
+// caller has waited for the calls in flight).
+static int moments_alloc(pnrt_ctx* c) {
+    (void)hipFree(c->moments);
+    c->moments = nullptr;
+    const size_t bytes = (size_t)c->width * c->height * 16;
+    HIPCHK(c, hipMalloc(&c->moments, bytes));
+    HIPCHK(c, hipMemsetAsync(c->moments, 0, bytes, c->stream));
+    return mark_stream(c);
+}
+
 extern "C" {
 
 #ifndef PNRT_SRC_HASH
@@ -973,6 +995,7 @@ void pnrt_destroy(pnrt_ctx* c) {
     for (float4* a : c->aov) (void)hipFree(a);
     (void)hipFree(c->g_primary); (void)hipFree(c->g_ovf); (void)hipFree(c->dn_guide);
     (void)hipFree(c->dn_img[0]); (void)hipFree(c->dn_img[1]);
+    (void)hipFree(c->moments); (void)hipFree(c->mom_err); (void)hipFree(c->mom_stats);
 
     for (auto& p : c->ev_pending) { c->ev_pool.push_back(p.second.first); c->ev_pool.push_back(p.second.second); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1438,6 +1461,8 @@ int pnrt_set_frame(pnrt_ctx* c, int w, int h, const pnrt_camera* cam, int depth)
         HIPCHK(c, hipMemsetAsync(c->accum, 0, (size_t)w * h * 16, c->stream));
         c->width = w; c->height = h;
         if (int rc = mark_stream(c)) return rc;
+        if (c->moments_ever)
+            if (int rc = moments_alloc(c)) return rc;
     }
     c->cam = *cam;
     c->max_bounce = depth;
@@ -1462,6 +1487,9 @@ int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int
     // frames after it would restart at 0: refused before anything is queued
     if ((uint64_t)first + nf > 0xFFFFFFFFull)
         return set_err(c, PNRT_E_ARG, "render: first_frame + n_frames exceeds 0xFFFFFFFF (the last frame number is 0xFFFFFFFE)");
+    // the one-kernel path keeps its frames in registers: no per-frame colours to take moments of
+    if (c->kernel == 1 && c->moments_on)
+        return set_err(c, PNRT_E_STATE, "render: PNRT_KERNEL_V1 cannot update the sample moments (pnrt_enable_moments(ctx, 0) first)");
     if (int rc = check_fault(c)) return rc;      // an earlier call's trace fault (completed work)
     if (nf == 0) return PNRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1527,6 +1555,7 @@ int pnrt_reset_accum(pnrt_ctx* c) {
     }
     if (!c->accum) return PNRT_OK;
     HIPCHK(c, hipMemsetAsync(c->accum, 0, (size_t)c->width * c->height * 16, c->stream));
+    if (c->moments) HIPCHK(c, hipMemsetAsync(c->moments, 0, (size_t)c->width * c->height * 16, c->stream));
     return mark_stream(c);
 }
 
@@ -1595,6 +1624,84 @@ int pnrt_read_denoised(pnrt_ctx* c, float* out) {
 }
 
 void* pnrt_denoised_device_ptr(pnrt_ctx* c) { return c ? c->dn_img[0] : nullptr; }
+
+int pnrt_enable_moments(pnrt_ctx* c, int on) {
+    if (!c) return PNRT_E_ARG;
+    if (on != 0 && on != 1) return set_err(c, PNRT_E_ARG, "enable_moments: on must be 0 or 1");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_all(c));                      // the calls in flight blend as they were issued
+    if (on && !c->moments && c->accum)           // (before pnrt_set_frame: allocated with the frame)
+        if (int rc = moments_alloc(c)) return rc;
+    if (on) c->moments_ever = true;
+    c->moments_on = on != 0;
+    return PNRT_OK;
+}
+
+void* pnrt_moments_device_ptr(pnrt_ctx* c) { return c ? c->moments : nullptr; }
+
+int pnrt_read_moments(pnrt_ctx* c, float* out) {
+    if (!c || !out) return PNRT_E_ARG;
+    if (!c->moments_ever) return set_err(c, PNRT_E_STATE, "read_moments: enable_moments first");
+    if (!c->moments) return set_err(c, PNRT_E_STATE, "read_moments: no frame");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->moments, (size_t)c->width * c->height * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, sync_all(c));
+    return check_fault(c);
+}
+
+int pnrt_read_error(pnrt_ctx* c, float* out) {
+    if (!c || !out) return PNRT_E_ARG;
+    if (!c->moments_ever) return set_err(c, PNRT_E_STATE, "read_error: enable_moments first");
+    if (!c->moments) return set_err(c, PNRT_E_STATE, "read_error: no frame");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t pix = (size_t)c->width * c->height;
+    if (pix > 0xFFFFFFFFull) return set_err(c, PNRT_E_ARG, "read_error: frame too large");
+    if (int rc = grow(c, (void**)&c->mom_err, &c->mom_err_cap, pix * 4)) return rc;
+    hipLaunchKernelGGL(pt_moments_error_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream,
+                       (const float4*)c->moments, c->mom_err, (uint32_t)pix);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, c->mom_err, pix * 4, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = mark_stream(c)) return rc;
+    HIPCHK(c, sync_all(c));
+    return check_fault(c);
+}
+
+int pnrt_convergence(pnrt_ctx* c, float threshold, int band, int nsh, int shard, pnrt_convergence_stats* out) {
+    if (!c || !out) return PNRT_E_ARG;
+    if (!std::isfinite(threshold) || !(threshold >= 0.0f))
+        return set_err(c, PNRT_E_ARG, "convergence: threshold must be finite and >= 0");
+    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "convergence: bad shard selector");
+    if (!c->moments_ever) return set_err(c, PNRT_E_STATE, "convergence: enable_moments first");
+    if (!c->moments) return set_err(c, PNRT_E_STATE, "convergence: no frame");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::memset(out, 0, sizeof *out);
+    const int rows = shard_rows(c->height, band, nsh, shard);
+    const size_t total = (size_t)rows * c->width;
+    MomentsStats st{};
+    if (total) {
+        // the identities of the record's atomics (static: the copy may read it after this call returns)
+        static const MomentsStats kIdentity = {0, 0, 0, 0, 0u, 0xFFFFFFFFu, 0u, 0u};
+        if (!c->mom_stats) HIPCHK(c, hipMalloc(&c->mom_stats, sizeof(MomentsStats)));
+        HIPCHK(c, hipMemcpyAsync(c->mom_stats, &kIdentity, sizeof kIdentity, hipMemcpyHostToDevice, c->stream));
+        const unsigned grid = (unsigned)std::min<size_t>((total + MOMENTS_REDUCE_BLOCK - 1) / MOMENTS_REDUCE_BLOCK, 2048);
+        hipLaunchKernelGGL(pt_moments_reduce_kernel, dim3(grid), dim3(MOMENTS_REDUCE_BLOCK), 0, c->stream,
+                           (const float4*)c->moments, c->mom_stats, c->width, rows, band, nsh, shard, threshold);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&st, c->mom_stats, sizeof st, hipMemcpyDeviceToHost, c->stream));
+        if (int rc = mark_stream(c)) return rc;
+    }
+    HIPCHK(c, sync_all(c));
+    if (total) {
+        out->n_pixels = (int64_t)st.n_pixels;
+        out->n_measured = (int64_t)st.n_measured;
+        out->n_above = (int64_t)st.n_above;
+        out->sum_q16 = (int64_t)st.sum_q16;
+        std::memcpy(&out->max_error, &st.max_error_bits, 4);
+        out->min_frames = st.min_frames;
+        out->max_frames = st.max_frames;
+    }
+    return check_fault(c);
+}
 
 int pnrt_profile_enable(pnrt_ctx* c, int on) {
     if (!c) return PNRT_E_ARG;

@@ -96,6 +96,26 @@ class InteractiveSession:
             self.frame_count += 1
         return depth, self.frame_count
 
+    def render_until(self, threshold: float, fraction: float = 0.95, max_frames: int = 1024, check_every: int = 8):
+        """``frame()`` after ``frame()`` until the image has converged: every pixel measured
+        (two frames or more) and at most ``1 - fraction`` of them with a relative standard
+        error above ``threshold`` -- asked of the library every ``check_every`` frames
+        (``PathTracer.convergence`` waits for the frames in flight) -- or until this call
+        has rendered ``max_frames`` frames.  Enables the sample moments itself.  Returns
+        (the last statistics -- None when ``max_frames`` left no check --, frames rendered)."""
+        if check_every < 1:
+            raise ValueError("render_until: check_every must be >= 1")
+        self.pt.enable_moments(True)
+        stats, done = None, 0
+        while done < max_frames:
+            self.frame()
+            done += 1
+            if done % check_every == 0 or done == max_frames:
+                stats = self.pt.convergence(threshold)
+                if stats["n_measured"] == stats["n_pixels"] and stats["n_above"] <= (1.0 - fraction) * stats["n_measured"]:
+                    break
+        return stats, done
+
     def preview(self, **params):
         """The denoised preview of the accumulation image as it stands (after ``frame()``,
         before the display: main.cpp:613 / :618-628).  The guide images are rendered only

@@ -216,6 +216,38 @@ class PathTracer:
     def denoised_ptr(self) -> int:
         return int(self._lib.pnrt_denoised_device_ptr(self._ctx) or 0)
 
+    # ---- sample moments and the convergence measure --------------------------------------
+    def enable_moments(self, on: bool = True):
+        """Keep per-pixel moments of the frames' luminance from now on (pnrt_enable_moments):
+        the blend of every ``render`` batch folds its frames in.  Waits for the calls in
+        flight; disabling keeps the image, enabling again keeps its data."""
+        self._ck(self._lib.pnrt_enable_moments(self._ctx, int(bool(on))), "pnrt_enable_moments")
+
+    def read_moments(self) -> np.ndarray:
+        """The moments image, (H, W, 4) float32, row 0 = bottom: mean luminance, M2, 0, and
+        the frame count n as uint32 bits (``m[..., 3].view(np.uint32)``)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self._lib.pnrt_read_moments(self._ctx, N.fptr(out)), "pnrt_read_moments")
+        return out
+
+    def read_error(self) -> np.ndarray:
+        """The clamped relative standard error of every pixel, (H, W) float32, +inf where
+        fewer than two frames were folded in (pnrt_read_error)."""
+        out = np.empty((self.height, self.width), np.float32)
+        self._ck(self._lib.pnrt_read_error(self._ctx, N.fptr(out)), "pnrt_read_error")
+        return out
+
+    def moments_ptr(self) -> int:
+        return int(self._lib.pnrt_moments_device_ptr(self._ctx) or 0)
+
+    def convergence(self, threshold: float, band: int = 1, n_shards: int = 1, shard: int = 0) -> dict:
+        """Statistics of the error over the rows of a shard selector (pnrt_convergence,
+        synchronous): the fields of ``pnrt_convergence_stats`` and ``mean_error``."""
+        st = N.ConvergenceStats()
+        self._ck(self._lib.pnrt_convergence(self._ctx, ctypes.c_float(threshold), band, n_shards, shard, ctypes.byref(st)),
+                 "pnrt_convergence")
+        return _with_mean_error({f: getattr(st, f) for f in CONVERGENCE_FIELDS})
+
     def pack_rows(self, dst_ptr: int, band: int, n_shards: int, shard: int):
         self._ck(self._lib.pnrt_pack_rows(self._ctx, ctypes.c_void_p(dst_ptr), band, n_shards, shard), "pnrt_pack_rows")
 
@@ -255,6 +287,27 @@ class PathTracer:
         out = np.empty_like(a)
         self._ck(self._lib.pnrt_debug_math(self._ctx, fn, N.fptr(a), N.fptr(b), N.fptr(out), len(a)), "pnrt_debug_math")
         return out
+
+
+CONVERGENCE_FIELDS = ("n_pixels", "n_measured", "n_above", "sum_q16", "max_error", "min_frames", "max_frames")
+
+
+def _with_mean_error(d: dict) -> dict:
+    d["mean_error"] = d["sum_q16"] / 65536 / d["n_measured"] if d["n_measured"] else 0.0
+    return d
+
+
+def merge_convergence(stats: list) -> dict:
+    """The statistics of the union of disjoint row sets from each set's own
+    (``PathTracer.convergence`` dicts): counts and ``sum_q16`` add, ``max_error`` and
+    ``max_frames`` take the max, ``min_frames`` the min -- over the sets that have
+    pixels (a set without rows reports zeros, which say nothing about the minimum)."""
+    some = [s for s in stats if s["n_pixels"]]
+    out = {k: sum(s[k] for s in some) for k in ("n_pixels", "n_measured", "n_above", "sum_q16")}
+    out["max_error"] = max((s["max_error"] for s in some), default=0.0)
+    out["min_frames"] = min((s["min_frames"] for s in some), default=0)
+    out["max_frames"] = max((s["max_frames"] for s in some), default=0)
+    return _with_mean_error(out)
 
 
 def shard_rows(height: int, band: int, n_shards: int, shard: int) -> np.ndarray:
