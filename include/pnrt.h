@@ -309,6 +309,43 @@ typedef struct {
 int pnrt_convergence(pnrt_ctx* ctx, float threshold, int band_rows, int n_shards, int shard,
                      pnrt_convergence_stats* out);
 
+/* Adaptive sampling (not in the reference, which renders every pixel every frame):
+ * render frames first_frame .. first_frame + n_frames - 1 only for the pixels of the
+ * selector's rows that have not converged.  The call waits for
+ * the calls in flight (as pnrt_enable_moments does), then evaluates once, on the
+ * moments image as it stands, with m = max(min_frames, 2):
+ *   a pixel is active iff n < m || e_c > threshold
+ * (n, e_c as pnrt_read_error computes them; an unmeasured pixel is active).  The mask
+ * holds for all batches of the call.  Tiles are 8x8 over (x, local row) of the
+ * selector; a tile is active iff one of its pixels is.
+ *   An active pixel receives every frame of the call -- the colour pnrt_render would
+ * produce for that pixel and frame, bit for bit -- folded in frame order: the moments
+ * update of pnrt_enable_moments, and the accumulation blended with
+ * a = 1.0f / (float)n, n the pixel's own count after the increment (pnrt_render uses
+ * 1.0f / (float)(frame + 1); the same for a pixel that got every frame since frame 0).
+ * An inactive pixel receives nothing: its accumulation and moments stay, bit for bit.
+ *   PNRT_E_STATE, and nothing queued: before pnrt_upload_scene / pnrt_set_frame; the
+ * moments never enabled or disabled; frames rendered by pnrt_render while the moments
+ * were disabled since they were last zeroed together with the accumulation
+ * (pnrt_reset_accum, a resize) or first enabled; PNRT_KERNEL_V1.  PNRT_E_ARG: a
+ * threshold that is not finite and >= 0, a bad selector, first_frame + n_frames >
+ * 0xFFFFFFFF.  PNRT_E_TRACE as pnrt_read_accum returns it.
+ *   n_frames == 0 evaluates the mask, fills `out` and queues nothing; so does a call
+ * without an active pixel.  After the mask step (one synchronisation) the call is
+ * asynchronous on the stream, like pnrt_render.  The batch plan (pnrt_batch_plan's
+ * rules) runs on 64 * n_active_tiles path slots per frame. */
+typedef struct {
+    int64_t  n_pixels;         /* pixels of the selector's rows                       */
+    int64_t  n_active_pixels;  /* ... that this call renders                          */
+    int64_t  n_tiles;          /* 8x8 tiles of the selector's rows (local-row tiling) */
+    int64_t  n_active_tiles;   /* ... with at least one active pixel                  */
+    uint32_t frames_per_batch, n_batches;   /* the plan the call ran (0, 0: nothing queued) */
+} pnrt_adaptive_stats;         /* 40 bytes */
+int pnrt_render_adaptive(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames,
+                         float threshold, uint32_t min_frames,
+                         int band_rows, int n_shards, int shard,
+                         pnrt_adaptive_stats* out /* may be NULL */);
+
 /* Per-kernel timing (not in the reference, which has no GPU timers): while
  * enabled, every launch of a kernel class is bracketed by HIP events recorded on
  * the launch stream; pnrt_profile_read synchronises and returns the summed

@@ -113,6 +113,12 @@ class ConvergenceStats(ctypes.Structure):
                 ("max_frames", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class AdaptiveStats(ctypes.Structure):
+    """``pnrt_adaptive_stats`` (40 bytes)."""
+    _fields_ = [("n_pixels", ctypes.c_int64), ("n_active_pixels", ctypes.c_int64), ("n_tiles", ctypes.c_int64),
+                ("n_active_tiles", ctypes.c_int64), ("frames_per_batch", ctypes.c_uint32), ("n_batches", ctypes.c_uint32)]
+
+
 def _sig(lib, name, res, *args):
     fn = getattr(lib, name)
     fn.restype = res
@@ -183,6 +189,8 @@ def _type_device(lib):
     _sig(lib, "pnrt_read_moments", INT, P, F)
     _sig(lib, "pnrt_read_error", INT, P, F)
     _sig(lib, "pnrt_convergence", INT, P, ctypes.c_float, INT, INT, INT, ctypes.POINTER(ConvergenceStats))
+    _sig(lib, "pnrt_render_adaptive", INT, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32, INT, INT, INT,
+         ctypes.POINTER(AdaptiveStats))
 
 
 def fptr(a) -> ctypes.POINTER(ctypes.c_float):

@@ -27,7 +27,8 @@ ARCH = os.environ.get("PNRT_OFFLOAD_ARCH", "gfx950")
 
 DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
-               "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pn_math.h", "sobol_v.inc"]
+               "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pt_adaptive.h", "pn_math.h",
+               "sobol_v.inc"]
 
 
 def _run(cmd, cwd=None):

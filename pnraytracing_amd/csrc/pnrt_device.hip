@@ -23,6 +23,7 @@
 #include "pt_bvh.h"
 #include "pt_denoise.h"
 #include "pt_moments.h"
+#include "pt_adaptive.h"
 
 __global__ void pt_pack_rows_kernel(const float4* accum, float4* dst, int width, int rows, int band,
                                     int n_shards, int shard) {
@@ -188,6 +189,13 @@ struct pnrt_ctx {
     float4* moments = nullptr;             // width * height records, as the accumulation image
     float* mom_err = nullptr;              size_t mom_err_cap = 0;     // pnrt_read_error's image
     MomentsStats* mom_stats = nullptr;     // pnrt_convergence's device record
+    // adaptive sampling (pnrt_render_adaptive; pt_adaptive.h): none until the first call
+    bool mom_cover = false;                // the moments count every frame the accumulation holds
+    unsigned long long* ad_masks = nullptr;  size_t ad_masks_cap = 0;  // per tile of the selector's rows: activity mask,
+    int* ad_flags = nullptr;               size_t ad_flags_cap = 0;    // "any pixel active" and its exclusive scan
+    int* ad_offs = nullptr;                size_t ad_offs_cap = 0;
+    WfTile* ad_list = nullptr;             size_t ad_list_cap = 0;     // the active-tile list
+    AdaptCounts* ad_counts = nullptr;      // the counts the host reads back
 };
 
 static int set_err(pnrt_ctx* c, int code, const std::string& m) {
@@ -205,7 +213,7 @@ static int check_fault(pnrt_ctx* c) {
             "diagnostic bounds check: a fetch / store index out of range at site "};
         static const char* site[] = {"?", "node", "triangle", "leaf table", "stack spill", "trace result", "ray record",
                                      "hit attributes", "light record", "env footprint", "albedo texel", "primary record",
-                                     "colour", "path state", "segment", "cooperative frontier"};
+                                     "colour", "path state", "segment", "cooperative frontier", "active-tile list"};
         std::string m;
         for (int k = 0; k < WF_FAULT_WORDS; ++k) {
             const uint32_t v = __atomic_load_n(c->fault_host + k, __ATOMIC_ACQUIRE);
@@ -482,7 +490,8 @@ static int report_trace_diag(pnrt_ctx* c, const WfBufs& b, hipStream_t st, int b
 // One batch of frames (gen -> {trace -> shade/setup} x depth) on one stream;
 // its colours land in frame slots [0, cf) of `colors`.
 static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const WfLayout& L, hipStream_t st,
-                        const float4* primary, float4* colors, bool alone, bool one, hipEvent_t stage = nullptr) {
+                        const float4* primary, float4* colors, bool alone, bool one, hipEvent_t stage = nullptr,
+                        const WfAdapt* ad = nullptr) {     // ad: an adaptive batch's slots (pt_adaptive.h)
     WfBufs b = L.b;
     if (b.n > WF_META_SLOT) return set_err(c, PNRT_E_ARG, "render: too many paths per batch");
     // the cooperative finish of closest-hit rays pays where the drain leaves the chip
@@ -497,7 +506,8 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
     if (WF_STATS) HIPCHK(c, hipMemsetAsync(b.stats + 56, 0, 64, st));    // the setups' moot-ray counts
     {   // path state + bounce-0 sampling
         ProfScope ps(c, PNRT_K_GEN, st);
-        hipLaunchKernelGGL(pt_wf_gen_setup, g, dim3(256), 0, st, s, fp, b, primary, colors);
+        if (ad) hipLaunchKernelGGL(pt_wf_gen_setup<WfAdapt>, g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
+        else hipLaunchKernelGGL(pt_wf_gen_setup<>, g, dim3(256), 0, st, s, fp, b, primary, colors);
     }
     HIPCHK(c, hipGetLastError());
     const unsigned tg = trace_grid_for(c, b.n, alone, one, cc && !s.has_leaf_table);
@@ -526,7 +536,12 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
             // MIS + continuation, then the next bounce's sampling (sets alternate)
             b.rd = L.set[bounce & 1];
             b.wr = L.set[(bounce + 1) & 1];
-            if (bounce + 1 == fp.max_depth)   // every path ends: no setup half, no rays
+            const bool fin = bounce + 1 == fp.max_depth;   // every path ends: no setup half, no rays
+            if (ad && fin)
+                hipLaunchKernelGGL((pt_wf_shade_setup<true, WfAdapt>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
+            else if (ad)
+                hipLaunchKernelGGL((pt_wf_shade_setup<false, WfAdapt>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
+            else if (fin)
                 hipLaunchKernelGGL(pt_wf_shade_setup<true>, g, dim3(256), 0, st, s, fp, b, primary, colors);
             else
                 hipLaunchKernelGGL(pt_wf_shade_setup<false>, g, dim3(256), 0, st, s, fp, b, primary, colors);
@@ -647,6 +662,76 @@ static int ensure_primary(pnrt_ctx* c, const DevScene& s, const FrameParams& fp,
     return PNRT_OK;
 }
 
+// A pipe's buffers for batches of `slots` path slots and `color_bytes` of frame colours
+// over a shard of `pix` pixels (render_wavefront, render_adaptive).
+static int pipe_size(pnrt_ctx* c, pnrt_ctx::Pipe& Q, size_t pix, size_t color_bytes, size_t slots, size_t ovf_bytes) {
+    int rc;
+    const float4* old_primary = Q.primary;
+    if ((rc = grow(c, (void**)&Q.primary, &Q.primary_cap, pix * 48)) ||
+        (rc = grow(c, (void**)&Q.colors, &Q.colors_cap, color_bytes)) ||
+        (rc = grow(c, &Q.wf, &Q.wf_cap, wf_bytes(slots) + 512)) ||
+        (rc = grow(c, (void**)&Q.ovf, &Q.ovf_cap, ovf_bytes)))
+        return rc;
+    if (Q.primary != old_primary) Q.prim.valid = false;
+    return PNRT_OK;
+}
+
+// How a call's batches run (render_wavefront decides it by call size and what is in
+// flight; render_adaptive is always a lone call).
+struct BatchRoute {
+    hipStream_t w;           // the stream of the batches' kernels (the caller's for a lone call)
+    bool alone, one, stagger;
+    int ovf_stride, tiles_x;
+    const WfAdapt* ad;       // an adaptive call's active-tile list, or null
+};
+// The batches of one call on pipe P: per group of `chunk` frames one batch (gen ->
+// {trace -> shade} x depth) of per_frame path slots per frame on R.w, then the
+// frame-ordered blend on the context stream.
+static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pnrt_ctx::Pipe& P, const BatchRoute& R,
+                       size_t per_frame, uint32_t chunk, uint32_t first, uint32_t nf) {
+    int rc;
+    const size_t pix = (size_t)fp.rows * c->width;
+    hipStream_t w = R.w;
+    for (uint32_t f0 = 0; f0 < nf; f0 += chunk) {
+        const uint32_t cf = (nf - f0) < chunk ? (nf - f0) : chunk;
+        WfLayout a = wf_layout(static_cast<char*>(P.wf), per_frame * cf);
+        a.b.ovf = P.ovf;
+        a.b.fault = c->fault_dev;
+        a.b.ovf_stride = (uint32_t)R.ovf_stride;
+        a.b.chunk_frames = (int)cf;
+        a.b.tiles_x = R.tiles_x;
+        a.b.first_frame = first + f0;
+        if (f0 && w != c->stream) HIPCHK(c, hipStreamWaitEvent(w, P.ev_blend, 0));   // the previous group's blend has read the colours
+        const bool last = f0 + cf >= nf;
+        if ((rc = render_batch(c, s, fp, a, w, P.primary, P.colors, R.alone, R.one, R.stagger && last ? P.ev_stage : nullptr,
+                               R.ad)))
+            return rc;
+        if (R.stagger && last) P.stage_set = true;
+        if (w != c->stream) {
+            HIPCHK(c, hipEventRecord(P.ev_join, w));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, P.ev_join, 0));
+        }
+        {   // the blends run in call order on the caller's stream
+            ProfScope ps(c, PNRT_K_BLEND);
+            if (R.ad)                   // the active pixels' blend and moments (pt_adaptive.h)
+                hipLaunchKernelGGL(pt_blend_adaptive_kernel, dim3((unsigned)(((size_t)R.ad->n_tiles * 64 + 255) / 256)), dim3(256),
+                                   0, c->stream, fp, *R.ad, R.tiles_x, (const float4*)P.colors, c->accum, c->moments, (int)cf,
+                                   first + f0);
+            else if (c->moments_on)     // the same blend, and the moments of the batch's frames (pt_moments.h)
+                hipLaunchKernelGGL(pt_blend_moments_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, fp,
+                                   (const float4*)P.colors, c->accum, c->moments, (int)cf, first + f0);
+            else
+                hipLaunchKernelGGL(pt_blend_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, fp,
+                                   (const float4*)P.colors, c->accum, (int)cf, first + f0);
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(P.ev_blend, c->stream));
+        P.blend_pending = true;
+        if ((rc = mark_stream(c))) return rc;
+    }
+    return PNRT_OK;
+}
+
 // v3 wavefront, one pnrt_render call on a pipe: the primary pass (unless the
 // pipe's records are still valid, PrimKey), then per group of <= WF_MAX_CHUNK_FRAMES frames one
 // batch (gen -> {trace -> shade} x depth) on the pipe's worker stream, then the
@@ -697,16 +782,8 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
     const size_t ovf_bytes = (size_t)c->trace_grid * WF_TRACE_BLOCK * ovf_stride * 8;
     // every buffer set this call size rotates over is sized now, so no later call of
     // the same size reallocates (a reallocation waits for all calls in flight)
-    for (unsigned q = 0; q < npipes; ++q) {
-        pnrt_ctx::Pipe& Q = c->pipe[(pi + q) % npipes];
-        const float4* old_primary = Q.primary;
-        if ((rc = grow(c, (void**)&Q.primary, &Q.primary_cap, pix * 48)) ||
-            (rc = grow(c, (void**)&Q.colors, &Q.colors_cap, pix * 16 * chunk)) ||
-            (rc = grow(c, &Q.wf, &Q.wf_cap, wf_bytes(per_frame * chunk) + 512)) ||
-            (rc = grow(c, (void**)&Q.ovf, &Q.ovf_cap, ovf_bytes)))
-            return rc;
-        if (Q.primary != old_primary) Q.prim.valid = false;
-    }
+    for (unsigned q = 0; q < npipes; ++q)
+        if ((rc = pipe_size(c, c->pipe[(pi + q) % npipes], pix, pix * 16 * chunk, per_frame * chunk, ovf_bytes))) return rc;
     ++c->ncall;
     // A call with nothing in flight runs on the caller's stream itself: no worker
     // stream to order against it, so no event wait before its first kernel and no
@@ -722,39 +799,31 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
     P.stage_set = false;
     // the pipe's primary records: traced now, or still valid from an earlier call (PrimKey)
     if ((rc = ensure_primary(c, s, fp, w, P.ovf, ovf_stride, P.primary, P.prim))) return rc;
-    for (uint32_t f0 = 0; f0 < nf; f0 += chunk) {
-        const uint32_t cf = (nf - f0) < chunk ? (nf - f0) : chunk;
-        WfLayout a = wf_layout(static_cast<char*>(P.wf), per_frame * cf);
-        a.b.ovf = P.ovf;
-        a.b.fault = c->fault_dev;
-        a.b.ovf_stride = (uint32_t)ovf_stride;
-        a.b.chunk_frames = (int)cf;
-        a.b.tiles_x = tiles_x;
-        a.b.first_frame = first + f0;
-        if (f0 && w != c->stream) HIPCHK(c, hipStreamWaitEvent(w, P.ev_blend, 0));   // the previous group's blend has read the colours
-        const bool last = f0 + cf >= nf;
-        if ((rc = render_batch(c, s, fp, a, w, P.primary, P.colors, alone, one, stagger && last ? P.ev_stage : nullptr)))
-            return rc;
-        if (stagger && last) P.stage_set = true;
-        if (w != c->stream) {
-            HIPCHK(c, hipEventRecord(P.ev_join, w));
-            HIPCHK(c, hipStreamWaitEvent(c->stream, P.ev_join, 0));
-        }
-        {   // the blends run in call order on the caller's stream
-            ProfScope ps(c, PNRT_K_BLEND);
-            if (c->moments_on)          // the same blend, and the moments of the batch's frames (pt_moments.h)
-                hipLaunchKernelGGL(pt_blend_moments_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, fp,
-                                   (const float4*)P.colors, c->accum, c->moments, (int)cf, first + f0);
-            else
-                hipLaunchKernelGGL(pt_blend_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, fp,
-                                   (const float4*)P.colors, c->accum, (int)cf, first + f0);
-        }
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(P.ev_blend, c->stream));
-        P.blend_pending = true;
-        if ((rc = mark_stream(c))) return rc;
-    }
-    return PNRT_OK;
+    const BatchRoute R = {w, alone, one, stagger, ovf_stride, tiles_x, nullptr};
+    return run_batches(c, s, fp, P, R, per_frame, chunk, first, nf);
+}
+
+// pnrt_render_adaptive's frames: the batches over the active tiles' path slots.  The
+// call has waited for everything in flight, so it is a lone call: the last call's pipe
+// (its primary records likely still valid, PrimKey), the caller's stream.
+static int render_adaptive(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const WfAdapt& ad, uint32_t chunk,
+                           uint32_t first, uint32_t nf) {
+    int rc;
+    if ((rc = pipes_init(c)) || (rc = trace_grid_init(c))) return rc;
+    const size_t pix = (size_t)fp.rows * c->width;
+    const size_t per_frame = (size_t)ad.n_tiles * 64;
+    const bool alone = !c->serial;
+    pnrt_ctx::Pipe& P = c->pipe[c->last_pipe < c->n_pipes_small ? c->last_pipe : 0];
+    c->last_pipe = (unsigned)(&P - c->pipe);
+    const int ovf_stride = c->wf_stack_need > WF_STACK ? c->wf_stack_need - WF_STACK : 1;
+    const size_t ovf_bytes = (size_t)c->trace_grid * WF_TRACE_BLOCK * ovf_stride * 8;
+    if ((rc = pipe_size(c, P, pix, per_frame * 16 * chunk, per_frame * chunk, ovf_bytes))) return rc;
+    ++c->ncall;
+    hipStream_t w = (alone && WF_ALONE_ON_CALLER) ? c->stream : P.w;
+    P.stage_set = false;
+    if ((rc = ensure_primary(c, s, fp, w, P.ovf, ovf_stride, P.primary, P.prim))) return rc;
+    const BatchRoute R = {w, alone, c->serial, false, ovf_stride, (c->width + 7) / 8, &ad};
+    return run_batches(c, s, fp, P, R, per_frame, chunk, first, nf);
 }
 
 static void free_env(pnrt_ctx* c);
@@ -904,6 +973,7 @@ static int moments_alloc(pnrt_ctx* c) {
     const size_t bytes = (size_t)c->width * c->height * 16;
     HIPCHK(c, hipMalloc(&c->moments, bytes));
     HIPCHK(c, hipMemsetAsync(c->moments, 0, bytes, c->stream));
+    c->mom_cover = true;             // first enabled, or zeroed with the accumulation (a resize)
     return mark_stream(c);
 }
 
@@ -996,6 +1066,8 @@ void pnrt_destroy(pnrt_ctx* c) {
     (void)hipFree(c->g_primary); (void)hipFree(c->g_ovf); (void)hipFree(c->dn_guide);
     (void)hipFree(c->dn_img[0]); (void)hipFree(c->dn_img[1]);
     (void)hipFree(c->moments); (void)hipFree(c->mom_err); (void)hipFree(c->mom_stats);
+    (void)hipFree(c->ad_masks); (void)hipFree(c->ad_flags); (void)hipFree(c->ad_offs); (void)hipFree(c->ad_list);
+    (void)hipFree(c->ad_counts);
 
     for (auto& p : c->ev_pending) { c->ev_pool.push_back(p.second.first); c->ev_pool.push_back(p.second.second); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1479,6 +1551,19 @@ static int shard_rows(int h, int band, int n, int shard) {
     return (int)rows;
 }
 
+// The frame parameters of a render call over a shard selector's rows.
+static FrameParams call_frame_params(const pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int shard) {
+    FrameParams fp;
+    std::memcpy(fp.eye, c->cam.eye, 12); std::memcpy(fp.llc, c->cam.lower_left, 12);
+    std::memcpy(fp.hor, c->cam.horizontal, 12); std::memcpy(fp.ver, c->cam.vertical, 12);
+    fp.width = c->width; fp.height = c->height; fp.max_depth = c->max_bounce;
+    fp.first_frame = first; fp.n_frames = nf;
+    fp.band = band; fp.n_shards = nsh; fp.shard = shard;
+    fp.rows = shard_rows(c->height, band, nsh, shard);
+    fp.mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
+    return fp;
+}
+
 int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int shard) {
     if (!c) return PNRT_E_ARG;
     if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, "render: upload_scene and set_frame first");
@@ -1492,15 +1577,9 @@ int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int
         return set_err(c, PNRT_E_STATE, "render: PNRT_KERNEL_V1 cannot update the sample moments (pnrt_enable_moments(ctx, 0) first)");
     if (int rc = check_fault(c)) return rc;      // an earlier call's trace fault (completed work)
     if (nf == 0) return PNRT_OK;
+    if (!c->moments_on) c->mom_cover = false;    // frames the moments do not count (pnrt_render_adaptive)
     HIPCHK(c, hipSetDevice(c->device));
-    FrameParams fp;
-    std::memcpy(fp.eye, c->cam.eye, 12); std::memcpy(fp.llc, c->cam.lower_left, 12);
-    std::memcpy(fp.hor, c->cam.horizontal, 12); std::memcpy(fp.ver, c->cam.vertical, 12);
-    fp.width = c->width; fp.height = c->height; fp.max_depth = c->max_bounce;
-    fp.first_frame = first; fp.n_frames = nf;
-    fp.band = band; fp.n_shards = nsh; fp.shard = shard;
-    fp.rows = shard_rows(c->height, band, nsh, shard);
-    fp.mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
+    const FrameParams fp = call_frame_params(c, first, nf, band, nsh, shard);
     if (fp.rows == 0) return PNRT_OK;
     DevScene s = launch_scene(c);
     if (WF_DIAG_BOUNDS) {                // the bounds check's own test (diagnostic builds only)
@@ -1555,7 +1634,10 @@ int pnrt_reset_accum(pnrt_ctx* c) {
     }
     if (!c->accum) return PNRT_OK;
     HIPCHK(c, hipMemsetAsync(c->accum, 0, (size_t)c->width * c->height * 16, c->stream));
-    if (c->moments) HIPCHK(c, hipMemsetAsync(c->moments, 0, (size_t)c->width * c->height * 16, c->stream));
+    if (c->moments) {
+        HIPCHK(c, hipMemsetAsync(c->moments, 0, (size_t)c->width * c->height * 16, c->stream));
+        c->mom_cover = true;         // zeroed together: the moments cover the accumulation again
+    }
     return mark_stream(c);
 }
 
@@ -1701,6 +1783,79 @@ int pnrt_convergence(pnrt_ctx* c, float threshold, int band, int nsh, int shard,
         out->max_frames = st.max_frames;
     }
     return check_fault(c);
+}
+
+int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float threshold, uint32_t min_frames, int band, int nsh,
+                         int shard, pnrt_adaptive_stats* out) {
+    if (!c) return PNRT_E_ARG;
+    if (!c->has_scene || !c->has_frame)
+        return set_err(c, PNRT_E_STATE, "render_adaptive: upload_scene and set_frame first");
+    if (!std::isfinite(threshold) || !(threshold >= 0.0f))
+        return set_err(c, PNRT_E_ARG, "render_adaptive: threshold must be finite and >= 0");
+    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "render_adaptive: bad shard selector");
+    if ((uint64_t)first + nf > 0xFFFFFFFFull)
+        return set_err(c, PNRT_E_ARG, "render_adaptive: first_frame + n_frames exceeds 0xFFFFFFFF (the last frame number is 0xFFFFFFFE)");
+    if (!c->moments_on || !c->moments)
+        return set_err(c, PNRT_E_STATE, "render_adaptive: the sample moments are not enabled (pnrt_enable_moments(ctx, 1) first)");
+    if (!c->mom_cover)
+        return set_err(c, PNRT_E_STATE, "render_adaptive: frames were rendered while the moments were disabled, so they do not "
+                                        "cover the accumulation (pnrt_reset_accum first)");
+    if (c->kernel == 1) return set_err(c, PNRT_E_STATE, "render_adaptive: PNRT_KERNEL_V1 has no per-frame colours");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_all(c));                      // the predicate reads the moments as every earlier call left them
+    if (int rc = check_fault(c)) return rc;
+    pnrt_adaptive_stats st{};
+    const FrameParams fp = call_frame_params(c, first, nf, band, nsh, shard);
+    const int tiles_x = (c->width + 7) / 8;
+    const size_t n_tiles = (size_t)tiles_x * (size_t)((fp.rows + 7) / 8);
+    st.n_pixels = (int64_t)fp.rows * c->width;
+    st.n_tiles = (int64_t)n_tiles;
+    WfAdapt ad{};
+    if (n_tiles) {
+        if (n_tiles > 0x7FFFFFFFull) return set_err(c, PNRT_E_ARG, "render_adaptive: frame too large");
+        int rc;
+        if ((rc = grow(c, (void**)&c->ad_masks, &c->ad_masks_cap, n_tiles * 8)) ||
+            (rc = grow(c, (void**)&c->ad_flags, &c->ad_flags_cap, n_tiles * 4)) ||
+            (rc = grow(c, (void**)&c->ad_offs, &c->ad_offs_cap, n_tiles * 4)) ||
+            (rc = grow(c, (void**)&c->ad_list, &c->ad_list_cap, n_tiles * sizeof(WfTile))))
+            return rc;
+        if (!c->ad_counts) HIPCHK(c, hipMalloc(&c->ad_counts, sizeof(AdaptCounts)));
+        // mask -> scan -> scatter, then the call's one synchronisation: the two counts
+        const uint32_t m = min_frames > 2u ? min_frames : 2u;
+        AdaptCounts cnt{};
+        HIPCHK(c, hipMemsetAsync(c->ad_counts, 0, sizeof(AdaptCounts), c->stream));
+        hipLaunchKernelGGL(pt_adaptive_mask_kernel, dim3((unsigned)((n_tiles + ADAPT_MASK_BLOCK / 64 - 1) / (ADAPT_MASK_BLOCK / 64))),
+                           dim3(ADAPT_MASK_BLOCK), 0, c->stream, (const float4*)c->moments, c->width, fp.rows, band, nsh, shard,
+                           tiles_x, (uint32_t)n_tiles, threshold, m, c->ad_masks, c->ad_flags);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(bvh_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const int*)c->ad_flags, c->ad_offs, (int)n_tiles);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(pt_adaptive_scatter_kernel, dim3((unsigned)((n_tiles + 255) / 256)), dim3(256), 0, c->stream,
+                           (const unsigned long long*)c->ad_masks, (const int*)c->ad_flags, (const int*)c->ad_offs,
+                           (uint32_t)n_tiles, c->ad_list, c->ad_counts);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&cnt, c->ad_counts, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+        if (int rc2 = mark_stream(c)) return rc2;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if ((size_t)cnt.n_active_tiles > n_tiles) return set_err(c, PNRT_E_HIP, "render_adaptive: the active-tile count is out of range");
+        st.n_active_pixels = (int64_t)cnt.n_active_pixels;
+        st.n_active_tiles = (int64_t)cnt.n_active_tiles;
+        ad.tiles = c->ad_list;
+        ad.n_tiles = cnt.n_active_tiles;
+    }
+    uint32_t chunk = 0;
+    if (nf > 0 && ad.n_tiles > 0) {
+        // the plan runs on the active tiles' slots: the colours are compact, 16 bytes per slot
+        const size_t per_frame = (size_t)ad.n_tiles * 64;
+        chunk = plan_chunk(c, per_frame, per_frame, nf);
+        if (chunk == 0) return set_err(c, PNRT_E_ARG, "render_adaptive: frame too large for one batch");
+        st.frames_per_batch = chunk;
+        st.n_batches = nf / chunk + (nf % chunk ? 1u : 0u);
+    }
+    if (out) *out = st;
+    if (chunk == 0) return PNRT_OK;              // nothing to render: nothing queued
+    DevScene s = launch_scene(c);
+    return render_adaptive(c, s, fp, ad, chunk, first, nf);
 }
 
 int pnrt_profile_enable(pnrt_ctx* c, int on) {

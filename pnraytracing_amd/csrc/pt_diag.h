@@ -91,5 +91,5 @@ PN_DEV long long pt_check_bound(uint32_t* fault, long long idx, long long n, int
 enum PtSite {
     PT_SITE_NODE = 1, PT_SITE_TRI, PT_SITE_LEAF_TABLE, PT_SITE_SPILL, PT_SITE_RESULT, PT_SITE_RAY,
     PT_SITE_HIT_ATTR, PT_SITE_LIGHT_REC, PT_SITE_ENV_QUAD, PT_SITE_TEXEL, PT_SITE_PRIMARY, PT_SITE_COLOR,
-    PT_SITE_PATH, PT_SITE_SEGMENT, PT_SITE_COOP
+    PT_SITE_PATH, PT_SITE_SEGMENT, PT_SITE_COOP, PT_SITE_TILE
 };

@@ -171,6 +171,38 @@ PN_DEV void wf_coords(const WfBufs& b, uint32_t s, int& x, int& lr, int& k) {
     lr = ty * 8 + (p >> 3);
 }
 
+// An adaptive batch (pnrt_render_adaptive, pt_adaptive.h) holds
+// paths of the active tiles only: entry a of the active-tile list, in increasing tile
+// order, names the tile and its 64-pixel activity mask, and
+//   slot = (a * chunk_frames + k) * 64 + p
+// is frame slot k of pixel p of that tile -- wf_coords with the list entry for the
+// tile.  The frame's colour is stored compact, at colors[slot].  The gen / shade
+// kernels take the mapping as a template argument (ADAPT): the default
+// instantiations never see the list.
+struct WfTile {
+    uint32_t tile, pad;
+    unsigned long long mask;     // bit p: pixel (p & 7, p >> 3) of the tile is active
+};
+struct WfAdapt {
+    const WfTile* tiles;
+    uint32_t n_tiles;            // entries of the list
+};
+// the kernels' trailing argument pack: nothing (no list), or the list
+PN_DEV WfAdapt wf_adapt() { return WfAdapt{nullptr, 0u}; }
+PN_DEV WfAdapt wf_adapt(const WfAdapt& ad) { return ad; }
+// -> whether the slot's pixel is active (a lane of an inactive pixel starts no path)
+PN_DEV bool wf_coords_adaptive(const WfBufs& b, const WfAdapt& ad, uint32_t s, int& x, int& lr, int& k) {
+    uint32_t per_tile = 64u * (uint32_t)b.chunk_frames;
+    uint32_t a = s / per_tile, rem = s - a * per_tile;
+    k = (int)(rem >> 6);
+    int p = (int)(rem & 63u);
+    const WfTile e = ad.tiles[PT_CHECK(b.fault, a, ad.n_tiles, PT_SITE_TILE)];
+    int ty = (int)(e.tile / (uint32_t)b.tiles_x), tx = (int)(e.tile - (uint32_t)ty * b.tiles_x);
+    x = tx * 8 + (p & 7);
+    lr = ty * 8 + (p >> 3);
+    return ((e.mask >> p) & 1ull) != 0ull;
+}
+
 // Number of set bits of m below this lane (v_mbcnt).
 PN_DEV uint32_t lanes_below(uint64_t m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -209,6 +241,18 @@ PN_DEV void wf_write_color(const WfBufs& b, const FrameParams& fp, float4* color
     const size_t at = PT_CHECK(b.fault, ((size_t)k * fp.rows + lr) * fp.width + x,
                                (size_t)b.chunk_frames * fp.rows * fp.width, PT_SITE_COLOR);
     ps_st(colors, at, make_float4(color.x, color.y, color.z, 0.f));
+}
+// ... of an adaptive batch: compact, at the path's slot
+PN_DEV void wf_write_color_adaptive(const WfBufs& b, float4* colors, uint32_t slot, f3 color) {
+    color = mk3(clampf(color.x, 0.f, 1.f), clampf(color.y, 0.f, 1.f), clampf(color.z, 0.f, 1.f));
+    const size_t at = PT_CHECK(b.fault, (size_t)slot, (size_t)b.n, PT_SITE_COLOR);
+    ps_st(colors, at, make_float4(color.x, color.y, color.z, 0.f));
+}
+// the colour of frame slot k of pixel (x, lr), the path of slot `slot`
+template <bool ADAPT>
+PN_DEV void wf_put_color(const WfBufs& b, const FrameParams& fp, float4* colors, uint32_t slot, int k, int lr, int x, f3 color) {
+    if constexpr (ADAPT) wf_write_color_adaptive(b, colors, slot, color);
+    else wf_write_color(b, fp, colors, k, lr, x, color);
 }
 // the primary record of local row lr, column x
 PN_DEV const float4* wf_primary(const WfBufs& b, const FrameParams& fp, const float4* primary, int lr, int x) {
@@ -585,8 +629,13 @@ PN_DEV void wf_enqueue(const WfBufs& b, uint32_t i, uint32_t nfl, const BounceRa
 #endif
 
 // ---- gen + bounce-0 setup: start every path from its pixel's primary hit -------------------
+// AD: empty (pt_wf_gen_setup<>, the slots of a pnrt_render batch: the kernel's five
+// arguments) or WfAdapt (the slots of an adaptive batch, through its list).
+template <class... AD>
 __global__ void __launch_bounds__(256, WF_GEN_WAVES) pt_wf_gen_setup(DevScene s, FrameParams fp, WfBufs b, const float4* primary,
-                                                       float4* colors) {
+                                                       float4* colors, AD... adv) {
+    constexpr bool ADAPT = sizeof...(AD) != 0;
+    const WfAdapt ad = wf_adapt(adv...);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;     // path slot
     wf_reset_counters(b);
     wf_live_init();
@@ -606,16 +655,18 @@ __global__ void __launch_bounds__(256, WF_GEN_WAVES) pt_wf_gen_setup(DevScene s,
     uint32_t frame = 0;
     if (i < b.n) {
         int lr, k;
-        wf_coords(b, i, x, lr, k);
-        if (x < fp.width && lr < fp.rows) {
+        bool active = true;
+        if constexpr (ADAPT) active = wf_coords_adaptive(b, ad, i, x, lr, k);    // (a clear mask bit: no path, no colour)
+        else wf_coords(b, i, x, lr, k);
+        if (active && x < fp.width && lr < fp.rows) {
             const float4* rec = wf_primary(b, fp, primary, lr, x);
             const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
             const int mt = __float_as_int(q0.w);
             const f3 base = mk3(q2.y, q2.z, q2.w);
             if (mt == -1) {                                   // primary miss: env colour only
-                wf_write_color(b, fp, colors, k, lr, x, base);
+                wf_put_color<ADAPT>(b, fp, colors, i, k, lr, x, base);
             } else if (fp.max_depth == 0) {
-                wf_write_color(b, fp, colors, k, lr, x, add(base, mk3(0.f, 0.f, 0.f)));
+                wf_put_color<ADAPT>(b, fp, colors, i, k, lr, x, add(base, mk3(0.f, 0.f, 0.f)));
             } else {
                 py = shard_row(lr, fp.band, fp.n_shards, fp.shard);
                 frame = b.first_frame + (uint32_t)k;
@@ -1806,7 +1857,8 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, PT_PRIM_WF_WAVES) pt_primary_w
 // ---- shade: MIS, continuation hit, next bounce or final colour (:936-972) --------------------
 // Path entry i of the read set.  Returns whether the path continues; then q,
 // bounce, slot and the pixel / frame carry its next bounce to the setup.
-PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs& b, const float4* primary,
+template <bool ADAPT>
+PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs& b, const WfAdapt& ad, const float4* primary,
                           float4* colors, uint32_t i, PathIn& q, int& bounce, uint32_t& slot, int& x, int& py,
                           uint32_t& frame) {
     const PathSet& rd = b.rd;
@@ -1841,14 +1893,15 @@ PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs
     f3 mis = add(muls(LE, pe), muls(LD, pl));
     Lo = add(Lo, muls(mul(cw, mis), invPDFSum));
     int lr, k;
-    wf_coords(b, slot, x, lr, k);
+    if constexpr (ADAPT) (void)wf_coords_adaptive(b, ad, slot, x, lr, k);     // (a path's pixel is active)
+    else wf_coords(b, slot, x, lr, k);
     if (ht < 0) {      // (a moot continuation ray -- NdotL = -1, WF_SKIP_MOOT -- is a miss that adds nothing)
         if (s.has_hdr && !(NdotL < 0.f)) {
             f3 enLi = env_color(s, normalize(L));
             Lo = add(Lo, divs(muls(mul(mul(cw, enLi), dBRDF), NdotL), dPDF));
         }
         const float4 q2 = wf_primary(b, fp, primary, lr, x)[2];     // the primary hit's base colour
-        wf_write_color(b, fp, colors, k, lr, x, add(mk3(q2.y, q2.z, q2.w), Lo));
+        wf_put_color<ADAPT>(b, fp, colors, slot, k, lr, x, add(mk3(q2.y, q2.z, q2.w), Lo));
         return false;
     }
     RayP r = make_ray(mk3(p0.x, p0.y, p0.z), L, 0);        // the continuation ray as traced
@@ -1859,7 +1912,7 @@ PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs
     ++bounce;
     if (bounce >= fp.max_depth) {
         const float4 q2 = wf_primary(b, fp, primary, lr, x)[2];
-        wf_write_color(b, fp, colors, k, lr, x, add(mk3(q2.y, q2.z, q2.w), Lo));
+        wf_put_color<ADAPT>(b, fp, colors, slot, k, lr, x, add(mk3(q2.y, q2.z, q2.w), Lo));
         return false;
     }
     // the next bounce starts here: its setup runs on the state in registers
@@ -1874,9 +1927,12 @@ PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs
 // ---- shade + next-bounce setup: MIS, continuation hit (:936-972), then the next
 // bounce's sampling for the paths that continue.  FINAL: the last bounce (every
 // path ends here), compiled without the setup half -> fewer registers, more waves.
-template <bool FINAL>
+// AD: as pt_wf_gen_setup's.
+template <bool FINAL, class... AD>
 __global__ void __launch_bounds__(256, FINAL ? 8 : WF_SHADE_WAVES) pt_wf_shade_setup(DevScene s, FrameParams fp, WfBufs b,
-                                                                     const float4* primary, float4* colors) {
+                                                                     const float4* primary, float4* colors, AD... adv) {
+    constexpr bool ADAPT = sizeof...(AD) != 0;
+    const WfAdapt ad = wf_adapt(adv...);
     // the block's live paths are its first b.rd.bcount[block] entries
     wf_check_drained(b);                      // (the previous trace's counters, then reset)
     if (!FINAL) wf_reset_counters(b);
@@ -1892,7 +1948,7 @@ __global__ void __launch_bounds__(256, FINAL ? 8 : WF_SHADE_WAVES) pt_wf_shade_s
     PathIn q;
     int bounce = 0, x = 0, py = 0;
     uint32_t slot = 0, frame = 0;
-    if (threadIdx.x < live) cont = wf_shade_path(s, fp, b, primary, colors, i, q, bounce, slot, x, py, frame);
+    if (threadIdx.x < live) cont = wf_shade_path<ADAPT>(s, fp, b, ad, primary, colors, i, q, bounce, slot, x, py, frame);
     if (FINAL) return;                        // bounce + 1 == max_depth: cont is false for every path
     const uint32_t j = blockIdx.x * 256u + wf_entry_rank(cont);
     uint32_t nfl = 0;

@@ -116,6 +116,28 @@ class InteractiveSession:
                     break
         return stats, done
 
+    def render_adaptive_until(self, threshold: float, max_frames: int = 1024, frames_per_call: int = 8, min_frames: int = 8):
+        """Adaptive calls of ``frames_per_call`` frames (the last one shorter), continuing
+        ``frame_count``, until a call finds no pixel active -- every pixel of the image has
+        ``max(min_frames, 2)`` frames and a relative standard error of at most ``threshold``
+        (``PathTracer.render_adaptive``) -- or until this call has issued ``max_frames``
+        frames.  Converged pixels receive no more frames.  Enables the sample moments
+        itself.  Returns (the last call's statistics -- None when ``max_frames`` left no
+        call --, frames issued)."""
+        if frames_per_call < 1:
+            raise ValueError("render_adaptive_until: frames_per_call must be >= 1")
+        self.pt.enable_moments(True)
+        stats, done = None, 0
+        while done < max_frames:
+            n = min(frames_per_call, max_frames - done)
+            self.pt.set_frame(self.width, self.height, self.camera.uniforms(), self.max_bounce_depth)
+            stats = self.pt.render_adaptive(self.frame_count, n, threshold, min_frames)
+            if stats["n_active_pixels"] == 0:        # nothing was rendered: the frames were not issued
+                break
+            self.frame_count += n
+            done += n
+        return stats, done
+
     def preview(self, **params):
         """The denoised preview of the accumulation image as it stands (after ``frame()``,
         before the display: main.cpp:613 / :618-628).  The guide images are rendered only

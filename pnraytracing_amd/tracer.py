@@ -248,6 +248,22 @@ class PathTracer:
                  "pnrt_convergence")
         return _with_mean_error({f: getattr(st, f) for f in CONVERGENCE_FIELDS})
 
+    def render_adaptive(self, first: int, n: int, threshold: float, min_frames: int = 8, band: int = 1, n_shards: int = 1,
+                        shard: int = 0) -> dict:
+        """Frames ``first .. first + n - 1`` for the pixels of the selector's rows that have
+        not converged (pnrt_render_adaptive): fewer than ``max(min_frames, 2)`` frames, or a
+        relative standard error above ``threshold``.  Needs the sample moments enabled since
+        the accumulation was last reset.  Waits for the calls in flight, evaluates the mask
+        once, then queues the frames like ``render``.  Returns the fields of
+        ``pnrt_adaptive_stats``; ``n = 0`` only asks how much is left."""
+        for name, v in (("first", first), ("n", n), ("min_frames", min_frames)):
+            if not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError(f"render_adaptive: {name} = {v} is outside 0 .. 2**32 - 1")
+        st = N.AdaptiveStats()
+        self._ck(self._lib.pnrt_render_adaptive(self._ctx, first, n, ctypes.c_float(threshold), min_frames, band, n_shards,
+                                                shard, ctypes.byref(st)), "pnrt_render_adaptive")
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
     def pack_rows(self, dst_ptr: int, band: int, n_shards: int, shard: int):
         self._ck(self._lib.pnrt_pack_rows(self._ctx, ctypes.c_void_p(dst_ptr), band, n_shards, shard), "pnrt_pack_rows")
 
