@@ -224,6 +224,44 @@ int pnrt_read_aov(pnrt_ctx* ctx, int which, float* rgba_out);
 /* Device pointer of a guide image (NULL before the first pnrt_render_guides). */
 void* pnrt_aov_device_ptr(pnrt_ctx* ctx, int which);
 
+/* Ray queries (not in the reference, whose only caller of BVHIntersect / BVHIntersectP
+ * is its shader, ray_tracing.comp:429-494): the closest hit, or any hit, of caller
+ * rays against the uploaded scene -- picking (which material is under this pixel, for
+ * pnrt_update_materials), visibility and probe rays.  The traversal is the renderer's:
+ * the same visit order, `>` tie rule (a later triangle at an equal distance wins) and
+ * traversal mode (pnrt_set_options), so a query sees what a rendered ray would.
+ *   rays7: n rays of 7 floats -- origin, direction, tMax -- 28 bytes apart.  The
+ * direction need not be normalised (time is in its units) and any tMax is taken as
+ * it is (tMax <= 0 hits nothing).  A ray with a float that is not finite, or with a
+ * direction of three zeros, is invalid: it is not traced and its record says so.
+ *   Rays are traced in the caller's order, 64 neighbours to a wavefront: coherent
+ * neighbours trace faster.
+ *   out: one 64-byte record per ray, words (floats as their bits):
+ *     0      hit: 1 or 0
+ *     1-3    position      4-6  normal (facing the ray, normalised)    7-8  texcoord
+ *     9      textureId (int32, -1 none)     10  materialId (int32)     11   time
+ *            -- words 1-11 are 0 without a hit, and for PNRT_QUERY_ANY
+ *     12     the ray's tMax afterwards: time on a closest hit, else as given
+ *     13     int32: the accepted triangle's index in the uploaded `triangles` array
+ *            (PNRT_QUERY_ANY: the triangle that ended the ray), -1 without a hit
+ *     14     flags: bit 0 = invalid ray (then every other word is 0, word 13 is -1)
+ *     15     0
+ * A query reads the scene only: the accumulation image, the moments, the guide
+ * images and the records pnrt_render keeps of the camera rays stay as they are, and
+ * pnrt_set_frame is not needed.  Its launches are timed as class PNRT_K_PRIMARY (as
+ * the guide images' own trace launch is).
+ *   PNRT_E_ARG: a kind other than the two, n < 0, a NULL pointer with n > 0.
+ * PNRT_E_STATE before pnrt_upload_scene.  n == 0 returns PNRT_OK and queues nothing. */
+#define PNRT_QUERY_CLOSEST 0
+#define PNRT_QUERY_ANY     1
+typedef struct { uint32_t w[16]; } pnrt_hit;   /* 64 bytes, layout above */
+/* Host arrays: copies the rays in (through buffers the context grows), queries,
+ * copies the records out and synchronises.  PNRT_E_TRACE as pnrt_read_accum returns it. */
+int pnrt_query_rays(pnrt_ctx* ctx, const float* rays7, int64_t n, int kind, pnrt_hit* out);
+/* Device arrays (rays7_dev 4-byte aligned; out_dev 16-byte aligned, else PNRT_E_ARG):
+ * asynchronous on the context's stream, ordered after everything already queued there. */
+int pnrt_query_rays_device(pnrt_ctx* ctx, const void* rays7_dev, int64_t n, int kind, void* out_dev);
+
 /* The denoised preview: the edge-avoiding a-trous wavelet filter (Dammertz et al.
  * 2010) over the accumulation image divided by max(albedo, 1/256), guided by the
  * normal and position images, multiplied by the albedo again -- a second image
@@ -350,7 +388,7 @@ int pnrt_render_adaptive(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames,
  * enabled, every launch of a kernel class is bracketed by HIP events recorded on
  * the launch stream; pnrt_profile_read synchronises and returns the summed
  * event durations (ms) and launch counts.  Enabling (or disabling) resets. */
-#define PNRT_K_PRIMARY 0   /* primary hits, one trace per pixel per render call */
+#define PNRT_K_PRIMARY 0   /* primary hits, one trace per pixel per render call; ray queries */
 #define PNRT_K_GEN 1       /* path state for the call's frames                  */
 #define PNRT_K_SETUP 2     /* per bounce: sampling + speculative BSDF, shadow rays */
 #define PNRT_K_TRACE 3     /* per bounce: persistent BVH traversal of all rays  */

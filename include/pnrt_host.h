@@ -91,6 +91,13 @@ int pnrt_scene_pack(const pnrt_scene* s, float* vertices, float* materials,
 int pnrt_camera_update(const float eye[3], const float center[3], const float up[3],
                        float fov_deg, float aspect, float out12[12]);
 
+/* CameraGetRay (ray_tracing.comp:205-211) for pixel (px, py), row 0 = bottom, as the
+ * renderer calls it: s = (float)px / (float)width, t = (float)py / (float)height, no
+ * jitter; cam12 = pnrt_camera_update's out12.  ray7_out: origin, normalised
+ * direction, tMax 1e7 -- a ray of libpnrt.so's pnrt_query_rays, bit for bit the one
+ * pnrt_render traces for that pixel (picking). */
+int pnrt_camera_pixel_ray(const float cam12[12], int px, int py, int width, int height, float ray7_out[7]);
+
 /* Camera state (camera.hpp:4-77) and the interactive controls that
  * main.cpp's mouse callbacks call (main.cpp:118-142): left drag ->
  * UpdateRotate(dx, dy), right drag -> UpdateTranslateUV(-dx, dy), scroll ->

@@ -119,6 +119,14 @@ class AdaptiveStats(ctypes.Structure):
                 ("n_active_tiles", ctypes.c_int64), ("frames_per_batch", ctypes.c_uint32), ("n_batches", ctypes.c_uint32)]
 
 
+QUERY_CLOSEST, QUERY_ANY = 0, 1                # PNRT_QUERY_*
+
+
+class Hit(ctypes.Structure):
+    """``pnrt_hit`` (64 bytes; the word layout is in include/pnrt.h)."""
+    _fields_ = [("w", ctypes.c_uint32 * 16)]
+
+
 def _sig(lib, name, res, *args):
     fn = getattr(lib, name)
     fn.restype = res
@@ -139,6 +147,7 @@ def _type_host(lib):
     _sig(lib, "pnrt_scene_set_bvh", INT, P, I32, F, INT, INT)
     _sig(lib, "pnrt_bvh_build_cpu", INT, F, INT, F, INT, PINT, I32, PINT)
     _sig(lib, "pnrt_camera_update", INT, F, F, F, ctypes.c_float, ctypes.c_float, F)
+    _sig(lib, "pnrt_camera_pixel_ray", INT, F, INT, INT, INT, INT, F)
     _sig(lib, "pnrt_hdr_decode_rgbe", INT, U8, ctypes.c_int64, PINT, PINT, F)
     _sig(lib, "pnrt_hdr_build_table", INT, F, INT, INT, F)
     _sig(lib, "pnrt_mesh_quad", INT, ctypes.c_float, F, F, F, I32, PINT, PINT)
@@ -191,6 +200,8 @@ def _type_device(lib):
     _sig(lib, "pnrt_convergence", INT, P, ctypes.c_float, INT, INT, INT, ctypes.POINTER(ConvergenceStats))
     _sig(lib, "pnrt_render_adaptive", INT, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32, INT, INT, INT,
          ctypes.POINTER(AdaptiveStats))
+    _sig(lib, "pnrt_query_rays", INT, P, F, ctypes.c_int64, INT, ctypes.POINTER(Hit))
+    _sig(lib, "pnrt_query_rays_device", INT, P, P, ctypes.c_int64, INT, P)
 
 
 def fptr(a) -> ctypes.POINTER(ctypes.c_float):

@@ -27,7 +27,7 @@ ARCH = os.environ.get("PNRT_OFFLOAD_ARCH", "gfx950")
 
 DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
-               "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pt_adaptive.h", "pn_math.h",
+               "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pt_adaptive.h", "pt_query.h", "pn_math.h",
                "sobol_v.inc"]
 
 
@@ -139,6 +139,12 @@ def build_abi_caller(force=False):
     vout = os.path.join(REPO, "tests", "abi", "c_abi_convergence")
     if os.path.exists(vsrc) and (force or _stale(vout, deps[1:2] + deps[3:4] + [vsrc])):
         _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, vsrc, "-o", vout, "-L", PKG, "-lpnrt",
+              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
+    # ray queries, both kinds, from a C translation unit (tests/test_gpu_query_c_abi.py)
+    qsrc = os.path.join(REPO, "tests", "abi", "c_abi_query.c")
+    qout = os.path.join(REPO, "tests", "abi", "c_abi_query")
+    if os.path.exists(qsrc) and (force or _stale(qout, deps[1:2] + deps[3:4] + [qsrc])):
+        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, qsrc, "-o", qout, "-L", PKG, "-lpnrt",
               "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
     # the multi-GPU caller: one process, one RCCL communicator per device (ncclCommInitAll + ncclGather)
     msrc = os.path.join(REPO, "tests", "abi", "c_abi_multigpu.cpp")

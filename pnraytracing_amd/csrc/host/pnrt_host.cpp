@@ -524,6 +524,22 @@ int pnrt_camera_update(const float e[3], const float c[3], const float up_[3], f
     return 0;
 }
 
+// CameraGetRay (ray_tracing.comp:205-211) as the renderer calls it for pixel (px, py),
+// row 0 = bottom (:980: no jitter): GLSL's normalize is v / sqrt(dot(v, v)), not glm's
+// v * inversesqrt; tMax is the shader's FLOAT_MAX.
+extern "C" int pnrt_camera_pixel_ray(const float cam[12], int px, int py, int width, int height, float out[7]) {
+    if (!cam || !out) return fail(-1, "camera_pixel_ray: null");
+    if (width <= 0 || height <= 0) return fail(-1, "camera_pixel_ray: empty frame");
+    const vec3 eye(cam[0], cam[1], cam[2]), llc(cam[3], cam[4], cam[5]), hor(cam[6], cam[7], cam[8]), ver(cam[9], cam[10], cam[11]);
+    const float s = (float)px / (float)width, t = (float)py / (float)height;
+    const vec3 d = ((llc + s * hor) + t * ver) - eye;
+    const float len = length(d);
+    out[0] = eye.x; out[1] = eye.y; out[2] = eye.z;
+    out[3] = d.x / len; out[4] = d.y / len; out[5] = d.z / len;
+    out[6] = 10000000.0f;
+    return 0;
+}
+
 // ---- Camera (camera.hpp:4-77): state + the interactive controls main.cpp's
 // mouse callbacks drive (main.cpp:118-142): left drag UpdateRotate, right drag
 // UpdateTranslateUV, scroll UpdateFov.  glm-exact float arithmetic.

@@ -24,6 +24,7 @@
 #include "pt_denoise.h"
 #include "pt_moments.h"
 #include "pt_adaptive.h"
+#include "pt_query.h"
 
 __global__ void pt_pack_rows_kernel(const float4* accum, float4* dst, int width, int rows, int band,
                                     int n_shards, int shard) {
@@ -196,6 +197,10 @@ struct pnrt_ctx {
     int* ad_offs = nullptr;                size_t ad_offs_cap = 0;
     WfTile* ad_list = nullptr;             size_t ad_list_cap = 0;     // the active-tile list
     AdaptCounts* ad_counts = nullptr;      // the counts the host reads back
+    // ray queries (pnrt_query_rays; pt_query.h): none until the first call
+    uint2* q_ovf = nullptr;                size_t q_ovf_cap = 0;       // the query kernel's stack spill area
+    float* q_rays = nullptr;               size_t q_rays_cap = 0;      // the host form's staging buffers: rays in,
+    uint4* q_out = nullptr;                size_t q_out_cap = 0;       // records out
 };
 
 static int set_err(pnrt_ctx* c, int code, const std::string& m) {
@@ -925,6 +930,55 @@ static int render_guides(pnrt_ctx* c) {
     return mark_stream(c);
 }
 
+// ---- ray queries (pt_query.h) ------------------------------------------------------------------
+// Rays of one launch at most (the kernel counts rays in 32 bits) and of one staging
+// pass of the host form (28 + 64 bytes of the context's buffers each).
+#define QUERY_MAX_LAUNCH ((int64_t)1 << 30)
+#define QUERY_MAX_STAGE ((int64_t)1 << 22)
+// Queue the query of n > 0 device rays into device records on the context stream: the
+// scene as it stands, the context's traversal mode, a spill area sized as the guides'
+// (render_guides).  Reads the scene only.  Launches of class PNRT_K_PRIMARY.
+static int query_launch(pnrt_ctx* c, const float* rays, int64_t n, int kind, uint4* out) {
+    int rc;
+    if ((rc = trace_grid_init(c))) return rc;
+    const DevScene s = launch_scene(c);
+    const int ovf_stride = c->wf_stack_need > WF_STACK ? c->wf_stack_need - WF_STACK : 1;
+    const size_t ovf_bytes = (size_t)c->trace_grid * WF_TRACE_BLOCK * ovf_stride * 8;
+    if ((rc = grow(c, (void**)&c->q_ovf, &c->q_ovf_cap, ovf_bytes))) return rc;
+    WfBufs qb{};
+    qb.ovf = c->q_ovf;
+    qb.fault = c->fault_dev;
+    qb.ovf_stride = (uint32_t)ovf_stride;
+    const int mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
+    const int any = kind == PNRT_QUERY_ANY;
+    for (int64_t at = 0; at < n; at += QUERY_MAX_LAUNCH) {
+        const uint32_t m = (uint32_t)std::min<int64_t>(n - at, QUERY_MAX_LAUNCH);
+        ProfScope ps(c, PNRT_K_PRIMARY, c->stream);
+        const unsigned g = (unsigned)std::min<size_t>(((size_t)m + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
+        if (s.has_leaf_table)
+            hipLaunchKernelGGL((pt_query_wf<WF_STACK, true>), dim3(g), dim3(WF_TRACE_BLOCK), 0, c->stream, s, qb, rays + 7 * at, m,
+                               any, mode, out + 4 * at);
+        else
+            hipLaunchKernelGGL((pt_query_wf<WF_STACK, false>), dim3(g), dim3(WF_TRACE_BLOCK), 0, c->stream, s, qb, rays + 7 * at, m,
+                               any, mode, out + 4 * at);
+        HIPCHK(c, hipGetLastError());
+    }
+    return mark_stream(c);
+}
+// The checks both forms share; PNRT_OK with *go = false for n == 0 (nothing to queue).
+static int query_check(pnrt_ctx* c, const void* rays, int64_t n, int kind, const void* out, bool* go) {
+    *go = false;
+    if (!c) return PNRT_E_ARG;
+    if (kind != PNRT_QUERY_CLOSEST && kind != PNRT_QUERY_ANY) return set_err(c, PNRT_E_ARG, "query_rays: unknown kind");
+    if (n < 0) return set_err(c, PNRT_E_ARG, "query_rays: n < 0");
+    if (n > 0 && (!rays || !out)) return set_err(c, PNRT_E_ARG, "query_rays: NULL rays or records");
+    if (!c->has_scene) return set_err(c, PNRT_E_STATE, "query_rays: upload_scene first");
+    if (n == 0) return PNRT_OK;
+    if (int rc = check_fault(c)) return rc;      // completed work that faulted
+    *go = true;
+    return PNRT_OK;
+}
+
 static int denoise(pnrt_ctx* c, const pnrt_denoise_params& p) {
     int rc;
     const size_t pix = (size_t)c->width * c->height;
@@ -1068,6 +1122,7 @@ void pnrt_destroy(pnrt_ctx* c) {
     (void)hipFree(c->moments); (void)hipFree(c->mom_err); (void)hipFree(c->mom_stats);
     (void)hipFree(c->ad_masks); (void)hipFree(c->ad_flags); (void)hipFree(c->ad_offs); (void)hipFree(c->ad_list);
     (void)hipFree(c->ad_counts);
+    (void)hipFree(c->q_ovf); (void)hipFree(c->q_rays); (void)hipFree(c->q_out);
 
     for (auto& p : c->ev_pending) { c->ev_pool.push_back(p.second.first); c->ev_pool.push_back(p.second.second); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1675,6 +1730,36 @@ int pnrt_read_aov(pnrt_ctx* c, int which, float* out) {
 
 void* pnrt_aov_device_ptr(pnrt_ctx* c, int which) {
     return (c && which >= 0 && which < PNRT_AOV_COUNT) ? c->aov[which] : nullptr;
+}
+
+int pnrt_query_rays_device(pnrt_ctx* c, const void* rays, int64_t n, int kind, void* out) {
+    bool go;
+    if (int rc = query_check(c, rays, n, kind, out, &go)) return rc;
+    if (!go) return PNRT_OK;
+    if (((uintptr_t)rays & 3u) || ((uintptr_t)out & 15u))
+        return set_err(c, PNRT_E_ARG, "query_rays_device: rays must be 4-byte aligned, records 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    return query_launch(c, static_cast<const float*>(rays), n, kind, static_cast<uint4*>(out));
+}
+
+int pnrt_query_rays(pnrt_ctx* c, const float* rays, int64_t n, int kind, pnrt_hit* out) {
+    bool go;
+    if (int rc = query_check(c, rays, n, kind, out, &go)) return rc;
+    if (!go) return PNRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t stage = std::min<int64_t>(n, QUERY_MAX_STAGE);
+    int rc;
+    if ((rc = grow(c, (void**)&c->q_rays, &c->q_rays_cap, (size_t)stage * 28)) ||
+        (rc = grow(c, (void**)&c->q_out, &c->q_out_cap, (size_t)stage * 64)))
+        return rc;
+    for (int64_t at = 0; at < n; at += stage) {
+        const int64_t m = std::min<int64_t>(n - at, stage);
+        HIPCHK(c, hipMemcpyAsync(c->q_rays, rays + 7 * at, (size_t)m * 28, hipMemcpyHostToDevice, c->stream));
+        if ((rc = query_launch(c, c->q_rays, m, kind, c->q_out))) return rc;
+        HIPCHK(c, hipMemcpyAsync(out + at, c->q_out, (size_t)m * 64, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, sync_all(c));
+    return check_fault(c);
 }
 
 int pnrt_denoise(pnrt_ctx* c, const pnrt_denoise_params* params) {

@@ -117,6 +117,17 @@ def camera_update(eye, center, up, fov: float, aspect: float) -> np.ndarray:
     return out.reshape(4, 3)
 
 
+def camera_pixel_ray(camera, px: int, py: int, width: int, height: int) -> np.ndarray:
+    """CameraGetRay for pixel (px, py), row 0 = bottom, as the renderer calls it
+    (pnrt_camera_pixel_ray): (7,) float32 = origin, normalised direction, tMax 1e7 --
+    a ray of ``PathTracer.query_rays``."""
+    cam = np.ascontiguousarray(camera, np.float32).reshape(12)
+    out = np.zeros(7, np.float32)
+    _check(N.host_lib().pnrt_camera_pixel_ray(N.fptr(cam), int(px), int(py), int(width), int(height), N.fptr(out)),
+           "camera_pixel_ray")
+    return out
+
+
 def decode_rgbe(data: bytes) -> np.ndarray:
     """stbi_loadf on a Radiance .hdr (3 channels, row 0 = first scanline)."""
     buf = np.frombuffer(data, np.uint8).copy()

@@ -138,6 +138,20 @@ class InteractiveSession:
             done += n
         return stats, done
 
+    def pick(self, px: int, py: int) -> dict:
+        """What is under pixel (px, py) -- row 0 = bottom, as ``PathTracer.read_aov`` --: the
+        decoded record (``tracer.decode_hits``, one ray: scalars and vectors) of the closest
+        hit of that pixel's camera ray, the ray ``frame()`` traces for it.  The selection
+        the reference's material panel makes from a combo box of names
+        (ImGuiLayer.hpp:37-49): ``pick(x, y)["material_id"]`` names the record
+        ``PathTracer.update_materials`` edits.  Changes no image."""
+        from .host import camera_pixel_ray
+        from .tracer import decode_hits
+        if not (0 <= px < self.width and 0 <= py < self.height):
+            raise ValueError(f"pick: pixel ({px}, {py}) is outside the {self.width}x{self.height} frame")
+        ray = camera_pixel_ray(self.camera.uniforms(), px, py, self.width, self.height)
+        return {k: v[0] for k, v in decode_hits(self.pt.query_rays(ray)).items()}
+
     def preview(self, **params):
         """The denoised preview of the accumulation image as it stands (after ``frame()``,
         before the display: main.cpp:613 / :618-628).  The guide images are rendered only

@@ -216,6 +216,27 @@ class PathTracer:
     def denoised_ptr(self) -> int:
         return int(self._lib.pnrt_denoised_device_ptr(self._ctx) or 0)
 
+    # ---- ray queries ---------------------------------------------------------------------
+    def query_rays(self, rays: np.ndarray, any_hit: bool = False) -> np.ndarray:
+        """The closest hit (or, with ``any_hit``, whether anything is hit) of caller rays
+        against the uploaded scene (pnrt_query_rays; synchronous): rays (n, 7) float32 =
+        origin, direction, tMax -> (n, 16) uint32 records, see ``decode_hits``.  The
+        renderer's own traversal; needs no ``set_frame`` and changes no image."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 7)
+        out = np.empty((len(r), 16), np.uint32)
+        self._ck(self._lib.pnrt_query_rays(self._ctx, N.fptr(r) if len(r) else None, len(r),
+                                           N.QUERY_ANY if any_hit else N.QUERY_CLOSEST,
+                                           out.ctypes.data_as(ctypes.POINTER(N.Hit)) if len(r) else None), "pnrt_query_rays")
+        return out
+
+    def query_rays_device(self, rays_ptr: int, n: int, out_ptr: int, any_hit: bool = False):
+        """The same from device memory into device memory (pnrt_query_rays_device):
+        ``rays_ptr`` n x 7 floats, ``out_ptr`` n x 64 bytes, 16-byte aligned.  Asynchronous
+        on the context's stream, after everything already queued there."""
+        self._ck(self._lib.pnrt_query_rays_device(self._ctx, ctypes.c_void_p(rays_ptr or 0), n,
+                                                  N.QUERY_ANY if any_hit else N.QUERY_CLOSEST, ctypes.c_void_p(out_ptr or 0)),
+                 "pnrt_query_rays_device")
+
     # ---- sample moments and the convergence measure --------------------------------------
     def enable_moments(self, on: bool = True):
         """Keep per-pixel moments of the frames' luminance from now on (pnrt_enable_moments):
@@ -303,6 +324,19 @@ class PathTracer:
         out = np.empty_like(a)
         self._ck(self._lib.pnrt_debug_math(self._ctx, fn, N.fptr(a), N.fptr(b), N.fptr(out), len(a)), "pnrt_debug_math")
         return out
+
+
+def decode_hits(records: np.ndarray) -> dict:
+    """The named fields of ``query_rays`` records ((n, 16) uint32, or one record): hit
+    (bool), position (n, 3), normal (n, 3), uv (n, 2), texture_id, material_id (int32), t
+    (the hit's time), t_max (the ray's tMax afterwards), triangle (int32 index into the
+    uploaded triangles, -1 without a hit), invalid (bool: a non-finite or zero-direction
+    ray, not traced).  Without a hit, and for an any-hit query, position .. t are zero."""
+    w = np.ascontiguousarray(records, np.uint32).reshape(-1, 16)
+    f, i = w.view(np.float32), w.view(np.int32)
+    return {"hit": w[:, 0] != 0, "position": f[:, 1:4], "normal": f[:, 4:7], "uv": f[:, 7:9],
+            "texture_id": i[:, 9], "material_id": i[:, 10], "t": f[:, 11], "t_max": f[:, 12],
+            "triangle": i[:, 13], "invalid": (w[:, 14] & 1) != 0}
 
 
 CONVERGENCE_FIELDS = ("n_pixels", "n_measured", "n_above", "sum_q16", "max_error", "min_frames", "max_frames")
