@@ -291,6 +291,37 @@ int pnrt_read_denoised(pnrt_ctx* ctx, float* rgba_out);
  * same pointer after every call at one frame size). */
 void* pnrt_denoised_device_ptr(pnrt_ctx* ctx);
 
+/* The variance-guided denoised preview: the same a-trous filter, guide images,
+ * pass-through rule and output image as pnrt_denoise, with the edge-stopping
+ * function of SVGF (Schied et al. 2017, section 4.4) in place of the global
+ * sigma_color.  A variance image is filtered alongside the colour; it starts as the
+ * variance of the mean luminance from the sample moments, in albedo-demodulated
+ * units, (M2 / (n - 1)) / n / lum(max(albedo, 1/256))^2, and as lum(c)^2 for an
+ * unmeasured pixel (n < 2).  In pass i a tap weighs
+ *   h * exp2(-(|lum(c_tap) - lum(c_centre)| / (sigma_variance * sqrt(g) + 2^-20)
+ *              + |dn|^2 / sigma_normal^2 + |dp|^2 / sigma_position^2))
+ * with g the 3x3 (1/4, 1/2, 1/4)^2 average, at unit spacing, of the variance around
+ * the centre, and the variance becomes sum(w^2 v) / (sum w)^2.  sigma_variance counts
+ * standard errors of the centre pixel and is not scaled per pass: a converged pixel
+ * is barely touched, a noisy one is smoothed hard.  Defined bit for bit (DESIGN.md
+ * section 24).  The filtered variance is not exposed.
+ * Writes the image pnrt_denoise writes: pnrt_read_denoised and
+ * pnrt_denoised_device_ptr serve both, the pointer is the same, and the image
+ * holds whichever filter ran last.  The accumulation and moments images are read
+ * and never written.  Asynchronous on the stream, ordered as pnrt_denoise.
+ * params == NULL: levels 5, sigma_variance 4, sigma_normal 0.25, sigma_position 0.5.
+ * (4 is the paper's sigma_l; it is not tuned here.)
+ * PNRT_E_ARG: levels outside 1..5, a sigma that is not finite and > 0 (the denoised
+ * image is left as it was).  PNRT_E_STATE: the sample moments were never enabled, or
+ * frames were rendered while they were disabled so that they do not cover the
+ * accumulation (as pnrt_render_adaptive refuses it); then every case of
+ * pnrt_denoise.  PNRT_E_TRACE as pnrt_pack_rows returns it. */
+typedef struct {
+    int levels;
+    float sigma_variance, sigma_normal, sigma_position;
+} pnrt_denoise_variance_params;   /* 16 bytes */
+int pnrt_denoise_variance(pnrt_ctx* ctx, const pnrt_denoise_variance_params* params);
+
 /* Per-pixel sample moments and a convergence measure (not in the reference, which
  * counts frames: main.cpp:628).  Opt-in: while enabled, the blend of every
  * pnrt_render batch also folds the batch's per-frame colours into a moments image,

@@ -106,6 +106,12 @@ class DenoiseParams(ctypes.Structure):
                 ("sigma_position", ctypes.c_float)]
 
 
+class DenoiseVarianceParams(ctypes.Structure):
+    """``pnrt_denoise_variance_params``."""
+    _fields_ = [("levels", ctypes.c_int), ("sigma_variance", ctypes.c_float), ("sigma_normal", ctypes.c_float),
+                ("sigma_position", ctypes.c_float)]
+
+
 class ConvergenceStats(ctypes.Structure):
     """``pnrt_convergence_stats`` (48 bytes)."""
     _fields_ = [("n_pixels", ctypes.c_int64), ("n_measured", ctypes.c_int64), ("n_above", ctypes.c_int64),
@@ -191,6 +197,7 @@ def _type_device(lib):
     _sig(lib, "pnrt_read_aov", INT, P, INT, F)
     _sig(lib, "pnrt_aov_device_ptr", P, P, INT)
     _sig(lib, "pnrt_denoise", INT, P, ctypes.POINTER(DenoiseParams))
+    _sig(lib, "pnrt_denoise_variance", INT, P, ctypes.POINTER(DenoiseVarianceParams))
     _sig(lib, "pnrt_read_denoised", INT, P, F)
     _sig(lib, "pnrt_denoised_device_ptr", P, P)
     _sig(lib, "pnrt_enable_moments", INT, P, INT)

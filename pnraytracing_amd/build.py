@@ -28,7 +28,7 @@ ARCH = os.environ.get("PNRT_OFFLOAD_ARCH", "gfx950")
 DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
                "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pt_adaptive.h", "pt_query.h", "pn_math.h",
-               "sobol_v.inc"]
+               "sobol_v.inc", "pt_denoise_var.h"]
 
 
 def _run(cmd, cwd=None):
@@ -145,6 +145,12 @@ def build_abi_caller(force=False):
     qout = os.path.join(REPO, "tests", "abi", "c_abi_query")
     if os.path.exists(qsrc) and (force or _stale(qout, deps[1:2] + deps[3:4] + [qsrc])):
         _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, qsrc, "-o", qout, "-L", PKG, "-lpnrt",
+              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
+    # the variance-guided preview from a C translation unit (tests/test_gpu_denoise_variance_c_abi.py)
+    dvsrc = os.path.join(REPO, "tests", "abi", "c_abi_denoise_variance.c")
+    dvout = os.path.join(REPO, "tests", "abi", "c_abi_denoise_variance")
+    if os.path.exists(dvsrc) and (force or _stale(dvout, deps[1:2] + deps[3:4] + [dvsrc])):
+        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, dvsrc, "-o", dvout, "-L", PKG, "-lpnrt",
               "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
     # the multi-GPU caller: one process, one RCCL communicator per device (ncclCommInitAll + ncclGather)
     msrc = os.path.join(REPO, "tests", "abi", "c_abi_multigpu.cpp")

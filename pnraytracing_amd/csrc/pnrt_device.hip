@@ -23,6 +23,7 @@
 #include "pt_bvh.h"
 #include "pt_denoise.h"
 #include "pt_moments.h"
+#include "pt_denoise_var.h"
 #include "pt_adaptive.h"
 #include "pt_query.h"
 
@@ -1019,6 +1020,45 @@ static int denoise(pnrt_ctx* c, const pnrt_denoise_params& p) {
     return mark_stream(c);
 }
 
+// pnrt_denoise_variance: the same images and ping-pong as denoise(), the kernels of pt_denoise_var.h
+static int denoise_variance(pnrt_ctx* c, const pnrt_denoise_variance_params& p) {
+    int rc;
+    const size_t pix = (size_t)c->width * c->height;
+    if ((rc = grow(c, (void**)&c->dn_guide, &c->dn_guide_cap, pix * 32)) ||
+        (rc = grow(c, (void**)&c->dn_img[0], &c->dn_img_cap[0], pix * 16)) ||
+        (rc = grow(c, (void**)&c->dn_img[1], &c->dn_img_cap[1], pix * 16)))
+        return rc;
+    DenoiseVarParams d{};
+    d.width = c->width; d.height = c->height;
+    d.sigma_v = p.sigma_variance;
+    d.inv_n = 1.0f / (p.sigma_normal * p.sigma_normal);
+    d.inv_p = 1.0f / (p.sigma_position * p.sigma_position);
+    const dim3 grid((unsigned)((c->width + 15) / 16), (unsigned)((c->height + 15) / 16));
+    const int first = p.levels & 1;      // the last pass writes dn_img[0]
+    // the moments are written by the blend launches, which this stream has queued before
+    hipLaunchKernelGGL(pt_denoise_var_prep, grid, dim3(256), 0, c->stream, d, c->scene.materials, c->scene.n_materials,
+                       (const float4*)c->accum, (const float4*)c->aov[PNRT_AOV_POSITION], (const float4*)c->aov[PNRT_AOV_NORMAL],
+                       (const float4*)c->aov[PNRT_AOV_ALBEDO], (const float4*)c->moments, c->dn_guide, c->dn_img[first]);
+    HIPCHK(c, hipGetLastError());
+    for (int i = 0; i < p.levels; ++i) {
+        d.step = 1 << i;
+        const float4* src = c->dn_img[(first + i) & 1];
+        float4* dst = c->dn_img[(first + i + 1) & 1];
+        const bool last = i + 1 == p.levels;
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, d, (const float4*)c->dn_guide, src, dst,
+                               (const float4*)c->accum, (const float4*)c->aov[PNRT_AOV_ALBEDO]);
+        };
+        if (d.step == 1) last ? launch(pt_denoise_var_pass_lds<1, true>) : launch(pt_denoise_var_pass_lds<1, false>);
+        else if (d.step == 2) last ? launch(pt_denoise_var_pass_lds<2, true>) : launch(pt_denoise_var_pass_lds<2, false>);
+        else if (d.step == 4) last ? launch(pt_denoise_var_pass_lds<4, true>) : launch(pt_denoise_var_pass_lds<4, false>);
+        else last ? launch(pt_denoise_var_pass<true>) : launch(pt_denoise_var_pass<false>);
+        HIPCHK(c, hipGetLastError());
+    }
+    c->dn_width = c->width; c->dn_height = c->height;
+    return mark_stream(c);
+}
+
 // A zeroed moments image of the current frame size, in place of the old one (the
 // caller has waited for the calls in flight).
 static int moments_alloc(pnrt_ctx* c) {
@@ -1777,6 +1817,31 @@ int pnrt_denoise(pnrt_ctx* c, const pnrt_denoise_params* params) {
     if (int rc = check_fault(c)) return rc;      // completed work that faulted
     HIPCHK(c, hipSetDevice(c->device));
     return denoise(c, p);
+}
+
+int pnrt_denoise_variance(pnrt_ctx* c, const pnrt_denoise_variance_params* params) {
+    if (!c) return PNRT_E_ARG;
+    pnrt_denoise_variance_params p = {5, 4.0f, 0.25f, 0.5f};      // the defaults (pnrt.h)
+    if (params) p = *params;
+    if (p.levels < 1 || p.levels > 5) return set_err(c, PNRT_E_ARG, "denoise_variance: levels must be 1..5");
+    for (float sg : {p.sigma_variance, p.sigma_normal, p.sigma_position})
+        if (!std::isfinite(sg) || !(sg > 0.0f))
+            return set_err(c, PNRT_E_ARG, "denoise_variance: every sigma must be finite and > 0");
+    if (!c->has_scene || !c->has_frame || !c->accum)
+        return set_err(c, PNRT_E_STATE, "denoise_variance: upload_scene and set_frame first");
+    if (!c->moments_ever || !c->moments)
+        return set_err(c, PNRT_E_STATE, "denoise_variance: the sample moments were never enabled (pnrt_enable_moments(ctx, 1) "
+                                        "before the frames are rendered)");
+    if (!c->mom_cover)
+        return set_err(c, PNRT_E_STATE, "denoise_variance: frames were rendered while the moments were disabled, so they do not "
+                                        "cover the accumulation (pnrt_reset_accum first)");
+    if (!c->guide_key.valid) return set_err(c, PNRT_E_STATE, "denoise_variance: render_guides first");
+    if (!guide_key_eq(c->guide_key, guide_key_now(c)))
+        return set_err(c, PNRT_E_STATE, "denoise_variance: the guide images are stale (camera, size, scene, materials, textures, "
+                                        "environment or traversal mode changed): render_guides again");
+    if (int rc = check_fault(c)) return rc;      // completed work that faulted
+    HIPCHK(c, hipSetDevice(c->device));
+    return denoise_variance(c, p);
 }
 
 int pnrt_read_denoised(pnrt_ctx* c, float* out) {

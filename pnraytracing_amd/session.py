@@ -166,3 +166,19 @@ class InteractiveSession:
                 raise
             self.pt.render_guides()
             self.pt.denoise(**params)
+
+    def preview_variance(self, **params):
+        """``preview()`` with the variance-guided filter (``PathTracer.denoise_variance``,
+        whose ``params`` these are).  The library checks the sample moments before the
+        guide images, so a PNRT_E_STATE that names ``render_guides`` is about the guides
+        alone: only then are they rendered and the filter tried again.  A PNRT_E_STATE
+        about the moments (never enabled, or not covering the accumulation) is raised
+        with its message."""
+        from .tracer import PnrtError
+        try:
+            self.pt.denoise_variance(**params)
+        except PnrtError as e:
+            if getattr(e, "code", 0) != -3 or "render_guides" not in str(e):
+                raise
+            self.pt.render_guides()
+            self.pt.denoise_variance(**params)

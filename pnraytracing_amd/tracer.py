@@ -22,6 +22,9 @@ SERIAL = 0x200         # | measurement: one call in flight, full trace grid (exc
 # pnrt_denoise(ctx, NULL)'s parameters (include/pnrt.h)
 DENOISE_DEFAULTS = {"levels": 5, "sigma_color": 2.0, "sigma_normal": 0.25, "sigma_position": 0.5}
 
+# pnrt_denoise_variance(ctx, NULL)'s parameters (include/pnrt.h)
+DENOISE_VARIANCE_DEFAULTS = {"levels": 5, "sigma_variance": 4.0, "sigma_normal": 0.25, "sigma_position": 0.5}
+
 
 class PnrtError(RuntimeError):
     pass
@@ -207,6 +210,21 @@ class PathTracer:
             p = N.DenoiseParams(*(d[k] if v is None else v for k, v in zip(d, given)))
             params = ctypes.byref(p)
         self._ck(self._lib.pnrt_denoise(self._ctx, params), "pnrt_denoise")
+
+    def denoise_variance(self, levels: int | None = None, sigma_variance: float | None = None,
+                         sigma_normal: float | None = None, sigma_position: float | None = None):
+        """The variance-guided a-trous preview into the same denoised image
+        (pnrt_denoise_variance); asynchronous.  ``sigma_variance`` counts standard errors of
+        the centre pixel, taken from the sample moments, which must cover the accumulation
+        (``enable_moments`` before the frames).  Arguments left out take the library's defaults."""
+        given = (levels, sigma_variance, sigma_normal, sigma_position)
+        if all(v is None for v in given):
+            params = None
+        else:
+            d = DENOISE_VARIANCE_DEFAULTS
+            p = N.DenoiseVarianceParams(*(d[k] if v is None else v for k, v in zip(d, given)))
+            params = ctypes.byref(p)
+        self._ck(self._lib.pnrt_denoise_variance(self._ctx, params), "pnrt_denoise_variance")
 
     def read_denoised(self) -> np.ndarray:
         out = np.empty((self.height, self.width, 4), np.float32)
