@@ -415,6 +415,63 @@ int pnrt_render_adaptive(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames,
                          int band_rows, int n_shards, int shard,
                          pnrt_adaptive_stats* out /* may be NULL */);
 
+/* Temporal reprojection (not in the reference, whose redraw starts the image again from
+ * one sample: main.cpp:592-596): after a camera move, resample the accumulation and the
+ * moments images from the view they were rendered with into the current one, so that the
+ * frames rendered before the move still count (bit for bit).
+ *   `from` is the camera the accumulation was rendered with; the current camera
+ * (pnrt_set_frame) is the one to reproject into.  Frame size, scene and traversal mode
+ * are the current ones: only the camera may differ.  Always the whole image: a context
+ * that rendered a shard has no whole image to resample, and sharded or multi-GPU
+ * reprojection is not provided.
+ *   Every pixel of the new view whose camera ray hits is projected into `from`'s image
+ * plane and takes the four bilinear taps there.  A tap counts only when it lies in the
+ * image, hits the same material, has dot(n_tap, n) >= normal_min and
+ * |P_tap - P|^2 <= (position_tolerance * |P - eye_from|)^2 (the guide images of both
+ * views), and holds at least one frame.  The pixel receives the taps' normalised blend of
+ * the colour, the mean luminance and the sample variance, and a frame count
+ * n' = min(the taps' smallest count, max_history); a hit without a valid tap (a
+ * disocclusion) and a primary miss start again at zero, colour and count.  The capped
+ * count bounds the weight of what was carried -- biased wherever shading depends on the
+ * view -- against the frames that follow.
+ *   Continue with pnrt_render_adaptive(first_frame >= 1, ...): its blend weighs every
+ * pixel by its own count, 1 / (float)n, so a disoccluded pixel takes the next frame whole
+ * and a long history takes it lightly.  pnrt_render stays legal and blends with its
+ * frame-number weight 1 / (float)(frame + 1), as ever, whatever the pixels' counts.
+ *   The call waits for the calls in flight (as pnrt_render_adaptive does) and is
+ * synchronous.  It needs the guide images of `from`: the current ones when they were
+ * rendered for it, else it renders them first (as pnrt_render_guides would, lent records
+ * included); their position and normal images are kept in two buffers of the context,
+ * allocated by the first call like the two images the result is written through.  Then it
+ * renders the guide images of the current camera: on return they are valid for it, and
+ * pnrt_denoise* needs no pnrt_render_guides.  pnrt_accum_device_ptr,
+ * pnrt_moments_device_ptr and pnrt_aov_device_ptr return what they returned before, the
+ * moments still cover the accumulation, and the records pnrt_render keeps of the camera
+ * rays are left alone.  Launches are timed as PNRT_K_PRIMARY (the guide traces) and
+ * PNRT_K_BLEND (the reprojection kernel and the copies).
+ *   PNRT_E_STATE, with nothing changed: before pnrt_upload_scene / pnrt_set_frame; the
+ * moments never enabled, disabled, or not covering the accumulation (the rule of
+ * pnrt_render_adaptive); PNRT_KERNEL_V1.  PNRT_E_ARG, with nothing changed: from NULL or
+ * one of its 12 floats not finite; normal_min not finite or outside [-1, 1];
+ * position_tolerance not finite or not > 0; max_history == 0; reserved != 0.
+ * PNRT_E_TRACE as pnrt_read_accum returns it. */
+typedef struct {
+    float    normal_min;          /* a tap needs dot(n_tap, n) >= normal_min      */
+    float    position_tolerance;  /* ... and |P_tap - P|^2 <= (tol * |P - eye_from|)^2 */
+    uint32_t max_history;         /* n' is at most this (>= 1)                    */
+    uint32_t reserved;            /* 0 */
+} pnrt_reproject_params;          /* 16 bytes; NULL: 0.9, 0.02, 32 */
+typedef struct {
+    int64_t  n_pixels;            /* width * height                               */
+    int64_t  n_reprojected;       /* pixels that received history (n' >= 1)       */
+    int64_t  n_disoccluded;       /* hits in the new view without a valid tap     */
+    int64_t  n_missed;            /* primary misses in the new view               */
+    int64_t  sum_frames;          /* sum of n' over the image                     */
+    uint32_t max_frames, reserved;
+} pnrt_reproject_stats;           /* 48 bytes */
+int pnrt_reproject(pnrt_ctx* ctx, const pnrt_camera* from,
+                   const pnrt_reproject_params* params, pnrt_reproject_stats* out /* may be NULL */);
+
 /* Per-kernel timing (not in the reference, which has no GPU timers): while
  * enabled, every launch of a kernel class is bracketed by HIP events recorded on
  * the launch stream; pnrt_profile_read synchronises and returns the summed

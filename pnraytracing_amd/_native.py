@@ -125,6 +125,19 @@ class AdaptiveStats(ctypes.Structure):
                 ("n_active_tiles", ctypes.c_int64), ("frames_per_batch", ctypes.c_uint32), ("n_batches", ctypes.c_uint32)]
 
 
+class ReprojectParams(ctypes.Structure):
+    """``pnrt_reproject_params`` (16 bytes)."""
+    _fields_ = [("normal_min", ctypes.c_float), ("position_tolerance", ctypes.c_float), ("max_history", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class ReprojectStats(ctypes.Structure):
+    """``pnrt_reproject_stats`` (48 bytes)."""
+    _fields_ = [("n_pixels", ctypes.c_int64), ("n_reprojected", ctypes.c_int64), ("n_disoccluded", ctypes.c_int64),
+                ("n_missed", ctypes.c_int64), ("sum_frames", ctypes.c_int64), ("max_frames", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
 QUERY_CLOSEST, QUERY_ANY = 0, 1                # PNRT_QUERY_*
 
 
@@ -207,6 +220,7 @@ def _type_device(lib):
     _sig(lib, "pnrt_convergence", INT, P, ctypes.c_float, INT, INT, INT, ctypes.POINTER(ConvergenceStats))
     _sig(lib, "pnrt_render_adaptive", INT, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32, INT, INT, INT,
          ctypes.POINTER(AdaptiveStats))
+    _sig(lib, "pnrt_reproject", INT, P, ctypes.POINTER(Camera), ctypes.POINTER(ReprojectParams), ctypes.POINTER(ReprojectStats))
     _sig(lib, "pnrt_query_rays", INT, P, F, ctypes.c_int64, INT, ctypes.POINTER(Hit))
     _sig(lib, "pnrt_query_rays_device", INT, P, P, ctypes.c_int64, INT, P)
 

@@ -26,6 +26,7 @@
 #include "pt_denoise_var.h"
 #include "pt_adaptive.h"
 #include "pt_query.h"
+#include "pt_reproject.h"
 
 __global__ void pt_pack_rows_kernel(const float4* accum, float4* dst, int width, int rows, int band,
                                     int n_shards, int shard) {
@@ -202,6 +203,12 @@ struct pnrt_ctx {
     uint2* q_ovf = nullptr;                size_t q_ovf_cap = 0;       // the query kernel's stack spill area
     float* q_rays = nullptr;               size_t q_rays_cap = 0;      // the host form's staging buffers: rays in,
     uint4* q_out = nullptr;                size_t q_out_cap = 0;       // records out
+    // temporal reprojection (pnrt_reproject; pt_reproject.h): none until the first call
+    float4* rp_pos = nullptr;              size_t rp_pos_cap = 0;      // the history: position and normal images of the
+    float4* rp_nrm = nullptr;              size_t rp_nrm_cap = 0;      // view the accumulation was rendered with
+    float4* rp_acc = nullptr;              size_t rp_acc_cap = 0;      // the resampled accumulation and moments, before
+    float4* rp_mom = nullptr;              size_t rp_mom_cap = 0;      // they are copied over the images themselves
+    ReprojectCounts* rp_counts = nullptr;  // the counts the host reads back
 };
 
 static int set_err(pnrt_ctx* c, int code, const std::string& m) {
@@ -854,12 +861,12 @@ static DevScene launch_scene(const pnrt_ctx* c) {
 }
 
 // ---- guide images and the denoised preview -------------------------------------------------
-// The camera and effective traversal mode of the current frame, as FrameParams
+// Camera `cam` and the effective traversal mode of the current frame, as FrameParams
 // of the whole image (one band, one shard).
-static FrameParams full_frame_params(const pnrt_ctx* c) {
+static FrameParams full_frame_params(const pnrt_ctx* c, const pnrt_camera& cam) {
     FrameParams fp;
-    std::memcpy(fp.eye, c->cam.eye, 12); std::memcpy(fp.llc, c->cam.lower_left, 12);
-    std::memcpy(fp.hor, c->cam.horizontal, 12); std::memcpy(fp.ver, c->cam.vertical, 12);
+    std::memcpy(fp.eye, cam.eye, 12); std::memcpy(fp.llc, cam.lower_left, 12);
+    std::memcpy(fp.hor, cam.horizontal, 12); std::memcpy(fp.ver, cam.vertical, 12);
     fp.width = c->width; fp.height = c->height; fp.max_depth = c->max_bounce;
     fp.first_frame = 0; fp.n_frames = 1;
     fp.band = 1; fp.n_shards = 1; fp.shard = 0;
@@ -867,28 +874,32 @@ static FrameParams full_frame_params(const pnrt_ctx* c) {
     fp.mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
     return fp;
 }
-// What guide images rendered now would be rendered for (pnrt_denoise compares).
-static pnrt_ctx::GuideKey guide_key_now(const pnrt_ctx* c) {
+// What guide images rendered now for camera `cam` would be rendered for.
+static pnrt_ctx::GuideKey guide_key_for(const pnrt_ctx* c, const pnrt_camera& cam) {
     pnrt_ctx::GuideKey k;
     k.epoch = c->scene_epoch;
     k.tex_epoch = c->tex_epoch;
-    std::memcpy(k.cam, c->cam.eye, 12); std::memcpy(k.cam + 3, c->cam.lower_left, 12);
-    std::memcpy(k.cam + 6, c->cam.horizontal, 12); std::memcpy(k.cam + 9, c->cam.vertical, 12);
+    std::memcpy(k.cam, cam.eye, 12); std::memcpy(k.cam + 3, cam.lower_left, 12);
+    std::memcpy(k.cam + 6, cam.horizontal, 12); std::memcpy(k.cam + 9, cam.vertical, 12);
     k.width = c->width; k.height = c->height;
     k.mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
     k.valid = true;
     return k;
 }
+// ... for the current camera (pnrt_denoise compares)
+static pnrt_ctx::GuideKey guide_key_now(const pnrt_ctx* c) { return guide_key_for(c, c->cam); }
 static bool guide_key_eq(const pnrt_ctx::GuideKey& a, const pnrt_ctx::GuideKey& b) {
     return a.valid && b.valid && a.epoch == b.epoch && a.tex_epoch == b.tex_epoch && !std::memcmp(a.cam, b.cam, sizeof a.cam) &&
            a.width == b.width && a.height == b.height && a.mode == b.mode;
 }
 
-static int render_guides(pnrt_ctx* c) {
+// The guide images of camera `cam` (the current one for pnrt_render_guides; the one the
+// accumulation was rendered with, then the current one, for pnrt_reproject).
+static int render_guides(pnrt_ctx* c, const pnrt_camera& cam) {
     int rc;
     if ((rc = pipes_init(c)) || (rc = trace_grid_init(c))) return rc;
     const DevScene s = launch_scene(c);
-    const FrameParams fp = full_frame_params(c);
+    const FrameParams fp = full_frame_params(c, cam);
     const size_t pix = (size_t)c->width * c->height;
     if (pix > 0xFFFFFFFFull / 64) return set_err(c, PNRT_E_ARG, "render_guides: frame too large");
     for (int k = 0; k < PNRT_AOV_COUNT; ++k)
@@ -927,7 +938,7 @@ static int render_guides(pnrt_ctx* c) {
                        c->aov[PNRT_AOV_POSITION], c->aov[PNRT_AOV_NORMAL], c->aov[PNRT_AOV_ALBEDO], (uint32_t)pix);
     HIPCHK(c, hipGetLastError());
     if (lender) HIPCHK(c, hipEventRecord(lender->ev_blend, c->stream));
-    c->guide_key = guide_key_now(c);
+    c->guide_key = guide_key_for(c, cam);
     return mark_stream(c);
 }
 
@@ -1163,6 +1174,8 @@ void pnrt_destroy(pnrt_ctx* c) {
     (void)hipFree(c->ad_masks); (void)hipFree(c->ad_flags); (void)hipFree(c->ad_offs); (void)hipFree(c->ad_list);
     (void)hipFree(c->ad_counts);
     (void)hipFree(c->q_ovf); (void)hipFree(c->q_rays); (void)hipFree(c->q_out);
+    (void)hipFree(c->rp_pos); (void)hipFree(c->rp_nrm); (void)hipFree(c->rp_acc); (void)hipFree(c->rp_mom);
+    (void)hipFree(c->rp_counts);
 
     for (auto& p : c->ev_pending) { c->ev_pool.push_back(p.second.first); c->ev_pool.push_back(p.second.second); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1752,7 +1765,7 @@ int pnrt_render_guides(pnrt_ctx* c) {
     if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, "render_guides: upload_scene and set_frame first");
     if (int rc = check_fault(c)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    return render_guides(c);
+    return render_guides(c, c->cam);
 }
 
 int pnrt_read_aov(pnrt_ctx* c, int which, float* out) {
@@ -2006,6 +2019,90 @@ int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float thresho
     if (chunk == 0) return PNRT_OK;              // nothing to render: nothing queued
     DevScene s = launch_scene(c);
     return render_adaptive(c, s, fp, ad, chunk, first, nf);
+}
+
+int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_params* params, pnrt_reproject_stats* out) {
+    if (!c) return PNRT_E_ARG;
+    if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, "reproject: upload_scene and set_frame first");
+    if (!c->moments_on || !c->moments)
+        return set_err(c, PNRT_E_STATE, "reproject: the sample moments are not enabled (pnrt_enable_moments(ctx, 1) first)");
+    if (!c->mom_cover)
+        return set_err(c, PNRT_E_STATE, "reproject: frames were rendered while the moments were disabled, so they do not "
+                                        "cover the accumulation (pnrt_reset_accum first)");
+    if (c->kernel == 1) return set_err(c, PNRT_E_STATE, "reproject: PNRT_KERNEL_V1 keeps no sample moments");
+    if (!from) return set_err(c, PNRT_E_ARG, "reproject: the camera the accumulation was rendered with is NULL");
+    for (const float* v : {from->eye, from->lower_left, from->horizontal, from->vertical})
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(v[k])) return set_err(c, PNRT_E_ARG, "reproject: a camera float is not finite");
+    pnrt_reproject_params p = {0.9f, 0.02f, 32u, 0u};        // the defaults (pnrt.h)
+    if (params) p = *params;
+    if (!std::isfinite(p.normal_min) || p.normal_min < -1.0f || p.normal_min > 1.0f)
+        return set_err(c, PNRT_E_ARG, "reproject: normal_min must be in [-1, 1]");
+    if (!std::isfinite(p.position_tolerance) || !(p.position_tolerance > 0.0f))
+        return set_err(c, PNRT_E_ARG, "reproject: position_tolerance must be finite and > 0");
+    if (p.max_history == 0u) return set_err(c, PNRT_E_ARG, "reproject: max_history must be >= 1");
+    if (p.reserved != 0u) return set_err(c, PNRT_E_ARG, "reproject: reserved must be 0");
+    const size_t pix = (size_t)c->width * c->height;
+    if (pix > 0xFFFFFFFFull / 64) return set_err(c, PNRT_E_ARG, "reproject: frame too large");     // (render_guides' limit)
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_all(c));                      // the images as every earlier call left them
+    int rc;
+    if ((rc = check_fault(c))) return rc;
+    if ((rc = grow(c, (void**)&c->rp_pos, &c->rp_pos_cap, pix * 16)) || (rc = grow(c, (void**)&c->rp_nrm, &c->rp_nrm_cap, pix * 16)) ||
+        (rc = grow(c, (void**)&c->rp_acc, &c->rp_acc_cap, pix * 16)) || (rc = grow(c, (void**)&c->rp_mom, &c->rp_mom_cap, pix * 16)))
+        return rc;
+    if (!c->rp_counts) HIPCHK(c, hipMalloc(&c->rp_counts, REPROJECT_SLOTS * sizeof(ReprojectCounts)));
+    // the guide images of `from` (the current ones when they were rendered for it), kept as the history
+    if (!guide_key_eq(c->guide_key, guide_key_for(c, *from)))
+        if ((rc = render_guides(c, *from))) return rc;
+    {
+        ProfScope ps(c, PNRT_K_BLEND);
+        HIPCHK(c, hipMemcpyAsync(c->rp_pos, c->aov[PNRT_AOV_POSITION], pix * 16, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->rp_nrm, c->aov[PNRT_AOV_NORMAL], pix * 16, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if ((rc = render_guides(c, c->cam))) return rc;
+    ReprojectArgs ra;
+    std::memcpy(ra.eye, from->eye, 12); std::memcpy(ra.llc, from->lower_left, 12);
+    std::memcpy(ra.hor, from->horizontal, 12); std::memcpy(ra.ver, from->vertical, 12);
+    ra.normal_min = p.normal_min; ra.position_tolerance = p.position_tolerance; ra.max_history = p.max_history;
+    ra.width = c->width; ra.height = c->height;
+    ra.tiles_x = (c->width + 7) / 8;
+    ra.n_tiles = (uint32_t)((size_t)ra.tiles_x * (size_t)((c->height + 7) / 8));      // <= pix: fits
+    std::vector<ReprojectCounts> slots(REPROJECT_SLOTS);
+    HIPCHK(c, hipMemsetAsync(c->rp_counts, 0, REPROJECT_SLOTS * sizeof(ReprojectCounts), c->stream));
+    {
+        ProfScope ps(c, PNRT_K_BLEND);
+        hipLaunchKernelGGL(pt_reproject_kernel, dim3(std::min<uint32_t>(ra.n_tiles, REPROJECT_MAX_GRID)), dim3(REPROJECT_BLOCK), 0,
+                           c->stream, ra, (const float4*)c->accum, (const float4*)c->moments, (const float4*)c->rp_pos,
+                           (const float4*)c->rp_nrm, (const float4*)c->aov[PNRT_AOV_POSITION],
+                           (const float4*)c->aov[PNRT_AOV_NORMAL], c->rp_acc, c->rp_mom, c->rp_counts);
+    }
+    HIPCHK(c, hipGetLastError());
+    {
+        ProfScope ps(c, PNRT_K_BLEND);
+        HIPCHK(c, hipMemcpyAsync(c->accum, c->rp_acc, pix * 16, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->moments, c->rp_mom, pix * 16, hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(slots.data(), c->rp_counts, REPROJECT_SLOTS * sizeof(ReprojectCounts), hipMemcpyDeviceToHost,
+                             c->stream));
+    if ((rc = mark_stream(c))) return rc;
+    HIPCHK(c, sync_all(c));
+    ReprojectCounts cnt{};                       // integers: the same whatever order the blocks arrived in
+    for (const ReprojectCounts& s : slots) {
+        cnt.n_reprojected += s.n_reprojected; cnt.n_disoccluded += s.n_disoccluded; cnt.n_missed += s.n_missed;
+        cnt.sum_frames += s.sum_frames;
+        cnt.max_frames = std::max(cnt.max_frames, s.max_frames);
+    }
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->n_pixels = (int64_t)pix;
+        out->n_reprojected = (int64_t)cnt.n_reprojected;
+        out->n_disoccluded = (int64_t)cnt.n_disoccluded;
+        out->n_missed = (int64_t)cnt.n_missed;
+        out->sum_frames = (int64_t)cnt.sum_frames;
+        out->max_frames = cnt.max_frames;
+    }
+    return check_fault(c);
 }
 
 int pnrt_profile_enable(pnrt_ctx* c, int on) {

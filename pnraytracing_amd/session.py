@@ -83,6 +83,7 @@ class InteractiveSession:
         self.camera = camera
         self.max_bounce_depth = max_bounce_depth
         self.frame_count = 0
+        self._rendered_camera = None                 # uniforms of the last call that rendered (reproject's `from`)
 
     def frame(self, redraw: bool = False, band: int = 1, n_shards: int = 1, shard: int = 0):
         if redraw:                                   # main.cpp:592-596
@@ -90,8 +91,10 @@ class InteractiveSession:
             self.frame_count = 0
         else:                                        # main.cpp:597-601
             depth = self.max_bounce_depth
-        self.pt.set_frame(self.width, self.height, self.camera.uniforms(), depth)
+        cam = self.camera.uniforms()
+        self.pt.set_frame(self.width, self.height, cam, depth)
         self.pt.render(self.frame_count, 1, band, n_shards, shard)   # main.cpp:612-613
+        self._rendered_camera = cam
         if not redraw:                               # main.cpp:628
             self.frame_count += 1
         return depth, self.frame_count
@@ -130,13 +133,45 @@ class InteractiveSession:
         stats, done = None, 0
         while done < max_frames:
             n = min(frames_per_call, max_frames - done)
-            self.pt.set_frame(self.width, self.height, self.camera.uniforms(), self.max_bounce_depth)
+            cam = self.camera.uniforms()
+            self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
             stats = self.pt.render_adaptive(self.frame_count, n, threshold, min_frames)
             if stats["n_active_pixels"] == 0:        # nothing was rendered: the frames were not issued
                 break
+            self._rendered_camera = cam
             self.frame_count += n
             done += n
         return stats, done
+
+    def reproject(self, **params) -> dict:
+        """After ``self.camera`` changed, in place of ``frame(redraw=True)``: carry the
+        accumulation and the sample moments over into the new view
+        (``PathTracer.reproject``, whose ``params`` these are) from the camera of the last
+        call that rendered.  Sets the frame to the new camera at the full bounce depth,
+        keeps ``frame_count`` and remembers the new camera, so moves chain.  Continue
+        with ``frame_counted()``.  Needs the sample moments enabled since the
+        accumulation was last reset (``frame_counted``, ``render_until`` and
+        ``render_adaptive_until`` enable them).  Returns the call's statistics."""
+        if self.frame_count == 0 or self._rendered_camera is None:
+            raise ValueError("reproject: nothing was rendered yet (frame_count == 0)")
+        cam = self.camera.uniforms()
+        self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
+        stats = self.pt.reproject(self._rendered_camera, **params)
+        self._rendered_camera = cam
+        return stats
+
+    def frame_counted(self, n: int = 1) -> dict:
+        """``n`` frames for every pixel, each blended at the weight of the pixel's own frame
+        count (one ``PathTracer.render_adaptive`` call with every pixel active): what
+        continues a reprojected image, whose pixels hold different counts.  Enables the
+        sample moments itself and advances ``frame_count`` by ``n``."""
+        self.pt.enable_moments(True)
+        cam = self.camera.uniforms()
+        self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
+        stats = self.pt.render_adaptive(self.frame_count, n, 0.0, 0xFFFFFFFF)
+        self._rendered_camera = cam
+        self.frame_count += n
+        return stats
 
     def pick(self, px: int, py: int) -> dict:
         """What is under pixel (px, py) -- row 0 = bottom, as ``PathTracer.read_aov`` --: the

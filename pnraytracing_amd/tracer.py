@@ -25,6 +25,9 @@ DENOISE_DEFAULTS = {"levels": 5, "sigma_color": 2.0, "sigma_normal": 0.25, "sigm
 # pnrt_denoise_variance(ctx, NULL)'s parameters (include/pnrt.h)
 DENOISE_VARIANCE_DEFAULTS = {"levels": 5, "sigma_variance": 4.0, "sigma_normal": 0.25, "sigma_position": 0.5}
 
+# pnrt_reproject(ctx, from, NULL, ...)'s parameters (include/pnrt.h)
+REPROJECT_DEFAULTS = {"normal_min": 0.9, "position_tolerance": 0.02, "max_history": 32}
+
 
 class PnrtError(RuntimeError):
     pass
@@ -302,6 +305,33 @@ class PathTracer:
         self._ck(self._lib.pnrt_render_adaptive(self._ctx, first, n, ctypes.c_float(threshold), min_frames, band, n_shards,
                                                 shard, ctypes.byref(st)), "pnrt_render_adaptive")
         return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def reproject(self, from_camera: np.ndarray, normal_min: float | None = None, position_tolerance: float | None = None,
+                  max_history: int | None = None) -> dict:
+        """After a camera move: resample the accumulation and the moments from the view
+        ``from_camera`` ((4, 3) uniforms, as ``set_frame`` takes them) they were rendered
+        with into the current camera (pnrt_reproject; synchronous, whole image).  History
+        of another surface is rejected through the guide images of both views; a
+        reprojected pixel keeps ``min(its taps' frame counts, max_history)`` frames, a
+        disoccluded or missed one starts at zero.  Continue with
+        ``render_adaptive(first >= 1, ...)``, which weighs every pixel by its own count.
+        Leaves the guide images valid for the current camera.  Arguments left out take
+        the library's defaults.  Returns the fields of ``pnrt_reproject_stats``."""
+        cam = N.Camera()
+        c = np.asarray(from_camera, np.float32).reshape(4, 3)
+        cam.eye[:], cam.lower_left[:], cam.horizontal[:], cam.vertical[:] = (list(map(float, r)) for r in c)
+        given = (normal_min, position_tolerance, max_history)
+        if all(v is None for v in given):
+            params = None
+        else:
+            if max_history is not None and not 0 <= max_history <= 0xFFFFFFFF:
+                raise ValueError(f"reproject: max_history = {max_history} is outside 0 .. 2**32 - 1")
+            d = REPROJECT_DEFAULTS
+            p = N.ReprojectParams(*(d[k] if v is None else v for k, v in zip(d, given)), 0)
+            params = ctypes.byref(p)
+        st = N.ReprojectStats()
+        self._ck(self._lib.pnrt_reproject(self._ctx, ctypes.byref(cam), params, ctypes.byref(st)), "pnrt_reproject")
+        return {f: getattr(st, f) for f, _ in st._fields_ if f != "reserved"}
 
     def pack_rows(self, dst_ptr: int, band: int, n_shards: int, shard: int):
         self._ck(self._lib.pnrt_pack_rows(self._ctx, ctypes.c_void_p(dst_ptr), band, n_shards, shard), "pnrt_pack_rows")
