@@ -472,6 +472,86 @@ typedef struct {
 int pnrt_reproject(pnrt_ctx* ctx, const pnrt_camera* from,
                    const pnrt_reproject_params* params, pnrt_reproject_stats* out /* may be NULL */);
 
+/* The display transform (not in the reference, whose render.frag shows the clamped
+ * accumulation, and whose GL blit stays out of scope): one of the context's float
+ * images to an 8-bit RGBA image on the device, with an exposure, a tone curve and a
+ * transfer function, so that a displayed frame copies width*height*4 bytes to the
+ * host instead of width*height*16 -- or none, through pnrt_display_device_ptr.
+ * Defined bit for bit; every product and sum below is rounded
+ * on its own.  For source pixel (x, y), row 0 = bottom, and each of r, g, b:
+ *   v = c * exposure;  s = (v > 0.0f) ? v : 0.0f   (NaN, negatives and -0 give +0)
+ *   s = fminf(s, 65536.0f)
+ *   PNRT_TONE_CLAMP     t = s
+ *   PNRT_TONE_REINHARD  w2 = white * white;  t = (s * (1.0f + s / w2)) / (1.0f + s)
+ *   PNRT_TONE_ACES      t = (s * (2.51f * s + 0.03f)) / (s * (2.43f * s + 0.59f) + 0.14f)
+ *   t = fminf(t, 1.0f)
+ *   PNRT_TRANSFER_LINEAR  u = t
+ *   PNRT_TRANSFER_SRGB    u = (t <= 0.0031308f) ? 12.92f * t : 1.055f * pow(t, e) - 0.055f,
+ *                         u = fminf(u, 1.0f); e the float 0x3ED55555 (1.0f / 2.4f), pow the
+ *                         library's own PN-libm pow (pnrt_debug_math fn 5)
+ *   q = (uint8_t)floorf(u * 255.0f + 0.5f)
+ * and alpha = 255.  The pixel goes to row height - 1 - y of the display image (top row
+ * first, as a PNG has it), or to row y with bottom_first = 1.  With params == NULL this
+ * is the reference's display: clamp, no gamma, top row first.
+ *   Asynchronous on the context's stream: ordered after the blends and filters already
+ * queued, and later calls that write the source are ordered after it (the rule of
+ * pnrt_denoise).  Reads its source and writes only the display image -- one RGBA8 image,
+ * allocated by the first call and again when the frame size has changed; the pointer is
+ * the same after every call at one frame size.  Launches are timed as PNRT_K_BLEND.
+ *   With an error nothing is queued and the display image is left as it was.
+ * PNRT_E_STATE: before pnrt_set_frame; PNRT_DISPLAY_DENOISED when no pnrt_denoise* has
+ * run at this frame size.  PNRT_E_ARG: an unknown source, tone or transfer; bottom_first
+ * not 0 or 1; exposure or white not finite or not > 0; PNRT_DISPLAY_EXTERNAL with a NULL
+ * or misaligned src_device.  PNRT_E_TRACE as pnrt_pack_rows returns it. */
+#define PNRT_DISPLAY_ACCUM    0   /* the accumulation image                          */
+#define PNRT_DISPLAY_DENOISED 1   /* the image pnrt_denoise / pnrt_denoise_variance wrote */
+#define PNRT_DISPLAY_EXTERNAL 2   /* src_device: width*height float4, row 0 = bottom, 16-byte aligned
+                                     (e.g. the gathered multi-GPU frame on rank 0)   */
+#define PNRT_TONE_CLAMP    0      /* the reference's display (render.frag: none)     */
+#define PNRT_TONE_REINHARD 1      /* extended Reinhard per channel, white point `white` */
+#define PNRT_TONE_ACES     2      /* Narkowicz's fitted ACES curve per channel       */
+#define PNRT_TRANSFER_LINEAR 0    /* the reference's (no gamma)                      */
+#define PNRT_TRANSFER_SRGB   1    /* the piecewise sRGB encoding                     */
+typedef struct {
+    int   source, tone, transfer, bottom_first;   /* bottom_first 0: top row first, as to_display and PNG */
+    float exposure, white;
+    const void* src_device;                       /* read only for PNRT_DISPLAY_EXTERNAL, else ignored */
+} pnrt_display_params;            /* 32 bytes; NULL: ACCUM, CLAMP, LINEAR, top first, exposure 1, white 4 */
+int pnrt_display(pnrt_ctx* ctx, const pnrt_display_params* params);
+/* Synchronise and copy the width*height*4 bytes of the display image to the host.
+ * PNRT_E_STATE before the first pnrt_display, or when the frame size has changed since. */
+int pnrt_read_display(pnrt_ctx* ctx, uint8_t* rgba8_out);
+/* Device pointer of the display image (NULL before the first pnrt_display). */
+void* pnrt_display_device_ptr(pnrt_ctx* ctx);
+
+/* Auto exposure: a histogram of the luminance of a display source over the rows of a
+ * shard selector (as pnrt_pack_rows takes it), and the exposure derived from it.
+ *   Y = ((0.2126f * c.x) + (0.7152f * c.y)) + (0.0722f * c.z) of the unexposed colour; a
+ * pixel is counted iff Y > 0 and Y is finite, in bin
+ *   clamp((int)(bits(Y) >> 19) - 1776, 0, 511)
+ * -- 16 bins per octave from the exponent and the top four mantissa bits, 2^-16 .. 2^16,
+ * 1.0 in bin 256, no libm.  n_pixels counts all pixels of the rows.  Every field is an
+ * integer combined with integer atomics, so the result does not depend on the order the
+ * blocks finish in, and histograms of disjoint selectors add up field by field (N ranks
+ * combine their own rows').  Synchronous; a shard without rows gives zeros.  The source
+ * is only read; the kernel is timed as PNRT_K_BLEND.  Errors as pnrt_display's for the
+ * source, and PNRT_E_ARG for a bad selector or a NULL `out`. */
+#define PNRT_LUMA_BINS 512
+typedef struct { int64_t n_pixels, n_counted; int64_t bins[PNRT_LUMA_BINS]; } pnrt_luma_histogram; /* 4112 bytes */
+int pnrt_luma_histogram_read(pnrt_ctx* ctx, int source, const void* src_device,
+                             int band_rows, int n_shards, int shard, pnrt_luma_histogram* out);
+/* Host only, no context: the exposure that brings the trimmed mean bin to `key`, in
+ * integer arithmetic.  N = n_counted; lo = N * low_permille / 1000, hi = N * high_permille
+ * / 1000; with cum_b the running sum of the bins, bin b contributes
+ * cnt_b = max(0, min(cum_b, hi) - max(cum_(b-1), lo)); S = sum cnt_b * b, C = sum cnt_b.
+ * C == 0: exposure 1.  Otherwise m = (2S + C) / (2C), k = 256 - m, e = floor(k / 16),
+ * j = k - 16e, exposure = key * ldexpf(T[j], e) with T[j] the float nearest 2^(j/16): a
+ * 1/16-stop grid, which also keeps the exposure from flickering frame to frame.
+ * PNRT_E_ARG: a NULL pointer, permille outside 0 <= low < high <= 1000, key not finite
+ * or not > 0. */
+int pnrt_exposure_from_histogram(const pnrt_luma_histogram* hist, int low_permille, int high_permille,
+                                 float key, float* exposure_out);
+
 /* Per-kernel timing (not in the reference, which has no GPU timers): while
  * enabled, every launch of a kernel class is bracketed by HIP events recorded on
  * the launch stream; pnrt_profile_read synchronises and returns the summed

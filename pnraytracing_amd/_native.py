@@ -138,6 +138,23 @@ class ReprojectStats(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+DISPLAY_SOURCES = ("accum", "denoised", "external")   # PNRT_DISPLAY_* order
+DISPLAY_TONES = ("clamp", "reinhard", "aces")         # PNRT_TONE_* order
+DISPLAY_TRANSFERS = ("linear", "srgb")                # PNRT_TRANSFER_* order
+LUMA_BINS = 512                                       # PNRT_LUMA_BINS
+
+
+class DisplayParams(ctypes.Structure):
+    """``pnrt_display_params`` (32 bytes)."""
+    _fields_ = [("source", ctypes.c_int), ("tone", ctypes.c_int), ("transfer", ctypes.c_int), ("bottom_first", ctypes.c_int),
+                ("exposure", ctypes.c_float), ("white", ctypes.c_float), ("src_device", ctypes.c_void_p)]
+
+
+class LumaHistogram(ctypes.Structure):
+    """``pnrt_luma_histogram`` (4112 bytes)."""
+    _fields_ = [("n_pixels", ctypes.c_int64), ("n_counted", ctypes.c_int64), ("bins", ctypes.c_int64 * LUMA_BINS)]
+
+
 QUERY_CLOSEST, QUERY_ANY = 0, 1                # PNRT_QUERY_*
 
 
@@ -221,6 +238,12 @@ def _type_device(lib):
     _sig(lib, "pnrt_render_adaptive", INT, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32, INT, INT, INT,
          ctypes.POINTER(AdaptiveStats))
     _sig(lib, "pnrt_reproject", INT, P, ctypes.POINTER(Camera), ctypes.POINTER(ReprojectParams), ctypes.POINTER(ReprojectStats))
+    _sig(lib, "pnrt_display", INT, P, ctypes.POINTER(DisplayParams))
+    _sig(lib, "pnrt_read_display", INT, P, U8)
+    _sig(lib, "pnrt_display_device_ptr", P, P)
+    _sig(lib, "pnrt_luma_histogram_read", INT, P, INT, P, INT, INT, INT, ctypes.POINTER(LumaHistogram))
+    _sig(lib, "pnrt_exposure_from_histogram", INT, ctypes.POINTER(LumaHistogram), INT, INT, ctypes.c_float,
+         ctypes.POINTER(ctypes.c_float))
     _sig(lib, "pnrt_query_rays", INT, P, F, ctypes.c_int64, INT, ctypes.POINTER(Hit))
     _sig(lib, "pnrt_query_rays_device", INT, P, P, ctypes.c_int64, INT, P)
 

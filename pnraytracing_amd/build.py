@@ -28,7 +28,7 @@ ARCH = os.environ.get("PNRT_OFFLOAD_ARCH", "gfx950")
 DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
                "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pt_adaptive.h", "pt_query.h", "pn_math.h",
-               "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h"]
+               "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h", "pt_display.h"]
 
 
 def _run(cmd, cwd=None):
@@ -157,6 +157,12 @@ def build_abi_caller(force=False):
     rout = os.path.join(REPO, "tests", "abi", "c_abi_reproject")
     if os.path.exists(rsrc) and (force or _stale(rout, deps[1:2] + deps[3:4] + [rsrc])):
         _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, rsrc, "-o", rout, "-L", PKG, "-lpnrt",
+              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
+    # the display transform and auto exposure from a C translation unit (tests/test_gpu_display_c_abi.py)
+    psrc = os.path.join(REPO, "tests", "abi", "c_abi_display.c")
+    pout = os.path.join(REPO, "tests", "abi", "c_abi_display")
+    if os.path.exists(psrc) and (force or _stale(pout, deps[1:2] + deps[3:4] + [psrc])):
+        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, psrc, "-o", pout, "-L", PKG, "-lpnrt",
               "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
     # the multi-GPU caller: one process, one RCCL communicator per device (ncclCommInitAll + ncclGather)
     msrc = os.path.join(REPO, "tests", "abi", "c_abi_multigpu.cpp")

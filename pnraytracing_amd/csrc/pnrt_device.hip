@@ -27,6 +27,7 @@
 #include "pt_adaptive.h"
 #include "pt_query.h"
 #include "pt_reproject.h"
+#include "pt_display.h"
 
 __global__ void pt_pack_rows_kernel(const float4* accum, float4* dst, int width, int rows, int band,
                                     int n_shards, int shard) {
@@ -209,6 +210,10 @@ struct pnrt_ctx {
     float4* rp_acc = nullptr;              size_t rp_acc_cap = 0;      // the resampled accumulation and moments, before
     float4* rp_mom = nullptr;              size_t rp_mom_cap = 0;      // they are copied over the images themselves
     ReprojectCounts* rp_counts = nullptr;  // the counts the host reads back
+    // the display transform (pnrt_display; pt_display.h): none until the first call
+    uint32_t* disp = nullptr;              // the RGBA8 display image
+    int disp_width = 0, disp_height = 0;   // its size (0: none yet)
+    LumaHist* luma_hist = nullptr;         // pnrt_luma_histogram_read's device record
 };
 
 static int set_err(pnrt_ctx* c, int code, const std::string& m) {
@@ -1176,6 +1181,7 @@ void pnrt_destroy(pnrt_ctx* c) {
     (void)hipFree(c->q_ovf); (void)hipFree(c->q_rays); (void)hipFree(c->q_out);
     (void)hipFree(c->rp_pos); (void)hipFree(c->rp_nrm); (void)hipFree(c->rp_acc); (void)hipFree(c->rp_mom);
     (void)hipFree(c->rp_counts);
+    (void)hipFree(c->disp); (void)hipFree(c->luma_hist);
 
     for (auto& p : c->ev_pending) { c->ev_pool.push_back(p.second.first); c->ev_pool.push_back(p.second.second); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -2103,6 +2109,155 @@ int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_pa
         out->max_frames = cnt.max_frames;
     }
     return check_fault(c);
+}
+
+// The image a display source names, or NULL with the error set (`what` names the caller).
+static const float4* display_source(pnrt_ctx* c, const char* what, int source, const void* src_device, int* rc) {
+    *rc = PNRT_OK;
+    const std::string w(what);
+    if (source != PNRT_DISPLAY_ACCUM && source != PNRT_DISPLAY_DENOISED && source != PNRT_DISPLAY_EXTERNAL) {
+        *rc = set_err(c, PNRT_E_ARG, w + ": unknown source");
+        return nullptr;
+    }
+    if (source == PNRT_DISPLAY_EXTERNAL && (!src_device || ((uintptr_t)src_device & 15u))) {
+        *rc = set_err(c, PNRT_E_ARG, w + ": PNRT_DISPLAY_EXTERNAL needs a 16-byte aligned src_device");
+        return nullptr;
+    }
+    if (!c->has_frame || !c->accum) {
+        *rc = set_err(c, PNRT_E_STATE, w + ": set_frame first");
+        return nullptr;
+    }
+    if ((size_t)c->width * c->height > 0x7FFFFFFFull) {
+        *rc = set_err(c, PNRT_E_ARG, w + ": frame too large");
+        return nullptr;
+    }
+    if (source == PNRT_DISPLAY_DENOISED) {
+        if (!c->dn_img[0] || c->dn_width != c->width || c->dn_height != c->height) {
+            *rc = set_err(c, PNRT_E_STATE, w + ": no denoised image of this frame size (pnrt_denoise or pnrt_denoise_variance first)");
+            return nullptr;
+        }
+        return c->dn_img[0];
+    }
+    return source == PNRT_DISPLAY_EXTERNAL ? static_cast<const float4*>(src_device) : c->accum;
+}
+
+int pnrt_display(pnrt_ctx* c, const pnrt_display_params* params) {
+    if (!c) return PNRT_E_ARG;
+    pnrt_display_params p = {PNRT_DISPLAY_ACCUM, PNRT_TONE_CLAMP, PNRT_TRANSFER_LINEAR, 0, 1.0f, 4.0f, nullptr};   // the defaults (pnrt.h)
+    if (params) p = *params;
+    if (p.tone != PNRT_TONE_CLAMP && p.tone != PNRT_TONE_REINHARD && p.tone != PNRT_TONE_ACES)
+        return set_err(c, PNRT_E_ARG, "display: unknown tone curve");
+    if (p.transfer != PNRT_TRANSFER_LINEAR && p.transfer != PNRT_TRANSFER_SRGB)
+        return set_err(c, PNRT_E_ARG, "display: unknown transfer");
+    if (p.bottom_first != 0 && p.bottom_first != 1) return set_err(c, PNRT_E_ARG, "display: bottom_first must be 0 or 1");
+    for (float v : {p.exposure, p.white})
+        if (!std::isfinite(v) || !(v > 0.0f)) return set_err(c, PNRT_E_ARG, "display: exposure and white must be finite and > 0");
+    int rc;
+    const float4* src = display_source(c, "display", p.source, p.src_device, &rc);
+    if (!src) return rc;
+    if ((rc = check_fault(c))) return rc;        // completed work that faulted
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t npix = (uint32_t)((size_t)c->width * c->height);
+    if (!c->disp || c->disp_width != c->width || c->disp_height != c->height) {
+        // the new image before the old one is freed: its pointer differs, and a failure leaves the old one
+        uint32_t* img = nullptr;
+        HIPCHK(c, hipMalloc(&img, (size_t)npix * 4));
+        if (c->disp) {
+            (void)sync_all(c);
+            (void)hipFree(c->disp);
+        }
+        c->disp = img;
+        c->disp_width = c->width; c->disp_height = c->height;
+    }
+    const float w2 = p.white * p.white;
+    const unsigned grid = (npix + DISPLAY_BLOCK * DISPLAY_PIXELS_PER_LANE - 1) / (DISPLAY_BLOCK * DISPLAY_PIXELS_PER_LANE);
+    // the source's writers (blends, filters) were queued on this stream before, its next writers come after
+    auto launch = [&](auto kernel) {
+        ProfScope ps(c, PNRT_K_BLEND);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(DISPLAY_BLOCK), 0, c->stream, src, c->disp, (uint32_t)c->width,
+                           (uint32_t)c->height, npix, p.bottom_first, p.exposure, w2);
+    };
+    const bool srgb = p.transfer == PNRT_TRANSFER_SRGB;
+    if (p.tone == PNRT_TONE_CLAMP) srgb ? launch(pt_display_kernel<DISPLAY_TONE_CLAMP, DISPLAY_TRANSFER_SRGB>)
+                                        : launch(pt_display_kernel<DISPLAY_TONE_CLAMP, DISPLAY_TRANSFER_LINEAR>);
+    else if (p.tone == PNRT_TONE_REINHARD) srgb ? launch(pt_display_kernel<DISPLAY_TONE_REINHARD, DISPLAY_TRANSFER_SRGB>)
+                                                : launch(pt_display_kernel<DISPLAY_TONE_REINHARD, DISPLAY_TRANSFER_LINEAR>);
+    else srgb ? launch(pt_display_kernel<DISPLAY_TONE_ACES, DISPLAY_TRANSFER_SRGB>)
+              : launch(pt_display_kernel<DISPLAY_TONE_ACES, DISPLAY_TRANSFER_LINEAR>);
+    HIPCHK(c, hipGetLastError());
+    return mark_stream(c);
+}
+
+int pnrt_read_display(pnrt_ctx* c, uint8_t* out) {
+    if (!c || !out) return PNRT_E_ARG;
+    if (!c->disp) return set_err(c, PNRT_E_STATE, "read_display: display first");
+    if (c->disp_width != c->width || c->disp_height != c->height)
+        return set_err(c, PNRT_E_STATE, "read_display: the display image has another size than the frame: display again");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->disp, (size_t)c->width * c->height * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, sync_all(c));
+    return check_fault(c);
+}
+
+void* pnrt_display_device_ptr(pnrt_ctx* c) { return c ? c->disp : nullptr; }
+
+int pnrt_luma_histogram_read(pnrt_ctx* c, int source, const void* src_device, int band, int nsh, int shard,
+                             pnrt_luma_histogram* out) {
+    if (!c || !out) return PNRT_E_ARG;
+    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "luma_histogram_read: bad shard selector");
+    int rc;
+    const float4* src = display_source(c, "luma_histogram_read", source, src_device, &rc);
+    if (!src) return rc;
+    if ((rc = check_fault(c))) return rc;        // completed work that faulted
+    HIPCHK(c, hipSetDevice(c->device));
+    static_assert(sizeof(LumaHist) == sizeof(pnrt_luma_histogram), "the device record is the public one");
+    std::memset(out, 0, sizeof *out);
+    const int rows = shard_rows(c->height, band, nsh, shard);
+    const size_t total = (size_t)rows * c->width;
+    if (total) {
+        if (!c->luma_hist) HIPCHK(c, hipMalloc(&c->luma_hist, sizeof(LumaHist)));
+        HIPCHK(c, hipMemsetAsync(c->luma_hist, 0, sizeof(LumaHist), c->stream));
+        const unsigned grid = (unsigned)std::min<size_t>((total + LUMA_HIST_BLOCK - 1) / LUMA_HIST_BLOCK, LUMA_HIST_MAX_BLOCKS);
+        {
+            ProfScope ps(c, PNRT_K_BLEND);
+            hipLaunchKernelGGL(pt_luma_hist_kernel, dim3(grid), dim3(LUMA_HIST_BLOCK), 0, c->stream, src, c->luma_hist,
+                               (uint32_t)c->width, (uint32_t)rows, band, nsh, shard);
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(out, c->luma_hist, sizeof(LumaHist), hipMemcpyDeviceToHost, c->stream));
+        if ((rc = mark_stream(c))) return rc;
+    }
+    HIPCHK(c, sync_all(c));
+    return check_fault(c);
+}
+
+// Host only: the exposure that puts the trimmed mean bin of the histogram at `key`
+// (DESIGN.md section 26), in integer arithmetic up to the one float multiply.
+int pnrt_exposure_from_histogram(const pnrt_luma_histogram* h, int low, int high, float key, float* exposure_out) {
+    if (!h || !exposure_out) return PNRT_E_ARG;
+    if (!(0 <= low && low < high && high <= 1000)) return PNRT_E_ARG;
+    if (!std::isfinite(key) || !(key > 0.0f)) return PNRT_E_ARG;
+    static const uint32_t kT[16] = {0x3F800000u, 0x3F85AAC3u, 0x3F8B95C2u, 0x3F91C3D3u, 0x3F9837F0u, 0x3F9EF532u,
+                                    0x3FA5FED7u, 0x3FAD583Fu, 0x3FB504F3u, 0x3FBD08A4u, 0x3FC5672Au, 0x3FCE248Cu,
+                                    0x3FD744FDu, 0x3FE0CCDFu, 0x3FEAC0C7u, 0x3FF5257Du};      // the floats nearest 2^(j/16)
+    const int64_t n = h->n_counted;
+    const int64_t lo = n * low / 1000, hi = n * high / 1000;
+    int64_t cum = 0, S = 0, C = 0;
+    for (int b = 0; b < PNRT_LUMA_BINS; ++b) {
+        const int64_t prev = cum;
+        cum += h->bins[b];
+        const int64_t cnt = std::min(cum, hi) - std::max(prev, lo);
+        if (cnt > 0) { S += cnt * b; C += cnt; }
+    }
+    if (C == 0) { *exposure_out = 1.0f; return PNRT_OK; }
+    const int m = (int)((2 * S + C) / (2 * C));
+    const int k = 256 - m;
+    const int e = k >= 0 ? k / 16 : -((-k + 15) / 16);
+    const int j = k - 16 * e;
+    float t;
+    std::memcpy(&t, &kT[j], 4);
+    *exposure_out = key * std::ldexp(t, e);
+    return PNRT_OK;
 }
 
 int pnrt_profile_enable(pnrt_ctx* c, int on) {

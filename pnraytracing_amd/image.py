@@ -26,6 +26,16 @@ def write_png(path: str, accum: np.ndarray) -> None:
     Image.fromarray(to_display(accum), "RGB").save(path)
 
 
+def write_png8(path: str, rgba8: np.ndarray) -> None:
+    """The display image (``PathTracer.read_display``: (H, W, 4) uint8, top row first,
+    alpha 255) as it is, without another conversion."""
+    from PIL import Image
+    a = np.asarray(rgba8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"write_png8: need an (H, W, 4) uint8 image, got {a.dtype} {a.shape}")
+    Image.fromarray(np.ascontiguousarray(a), "RGBA").save(path)
+
+
 def write_pfm(path: str, accum: np.ndarray) -> None:
     """Little-endian RGB PFM, bottom row first (lossless float32)."""
     a = np.ascontiguousarray(np.asarray(accum, np.float32)[:, :, :3], "<f4")

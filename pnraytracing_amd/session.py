@@ -202,6 +202,22 @@ class InteractiveSession:
             self.pt.render_guides()
             self.pt.denoise(**params)
 
+    def show(self, denoised: bool = False, auto_exposure: bool = False, **display_params) -> np.ndarray:
+        """The frame as a screen takes it (main.cpp:618-628's display, converted on the
+        device): the accumulation image -- or, with ``denoised``, the preview that
+        ``preview()`` / ``preview_variance()`` wrote -- through ``PathTracer.display``, whose
+        ``display_params`` these are (tone, transfer, exposure, white, bottom_first), read
+        back as (H, W, 4) uint8.  With ``auto_exposure`` the luminance histogram of the
+        shown image is taken first and the exposure derived from it
+        (``tracer.exposure_from_histogram`` at its defaults), in place of any ``exposure``
+        given."""
+        from .tracer import exposure_from_histogram
+        source = "denoised" if denoised else "accum"
+        if auto_exposure:
+            display_params["exposure"] = exposure_from_histogram(self.pt.luma_histogram(source))
+        self.pt.display(source=source, **display_params)
+        return self.pt.read_display()
+
     def preview_variance(self, **params):
         """``preview()`` with the variance-guided filter (``PathTracer.denoise_variance``,
         whose ``params`` these are).  The library checks the sample moments before the

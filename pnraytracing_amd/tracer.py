@@ -237,8 +237,53 @@ class PathTracer:
     def denoised_ptr(self) -> int:
         return int(self._lib.pnrt_denoised_device_ptr(self._ctx) or 0)
 
+    # ---- the display transform and auto exposure ------------------------------------------
+    @staticmethod
+    def _enum(what, names, v) -> int:
+        if isinstance(v, str):
+            if v not in names:
+                raise ValueError(f"unknown {what} {v!r}: one of {names}")
+            return names.index(v)
+        return int(v)
+
+    def display(self, source="accum", tone="clamp", transfer="linear", exposure: float = 1.0, white: float = 4.0,
+                bottom_first: bool = False, src_ptr: int | None = None):
+        """One of the float images to the 8-bit RGBA display image on the device
+        (pnrt_display; asynchronous): ``source`` ``"accum"``, ``"denoised"`` or ``"external"``
+        (then ``src_ptr``: a device image of width*height float4, row 0 = bottom), times
+        ``exposure``, through the ``tone`` curve ``"clamp"``, ``"reinhard"`` (white point
+        ``white``) or ``"aces"`` and the ``transfer`` ``"linear"`` or ``"srgb"``.  The
+        defaults are the reference's display, ``image.to_display`` plus alpha."""
+        p = N.DisplayParams(self._enum("display source", N.DISPLAY_SOURCES, source),
+                            self._enum("tone curve", N.DISPLAY_TONES, tone),
+                            self._enum("transfer", N.DISPLAY_TRANSFERS, transfer),
+                            int(bottom_first), exposure, white, ctypes.c_void_p(src_ptr or 0))
+        self._ck(self._lib.pnrt_display(self._ctx, ctypes.byref(p)), "pnrt_display")
+
+    def read_display(self) -> np.ndarray:
+        """The display image, (H, W, 4) uint8, alpha 255; top row first unless the last
+        ``display`` asked for ``bottom_first`` (pnrt_read_display; synchronises)."""
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        self._ck(self._lib.pnrt_read_display(self._ctx, N.u8ptr(out)), "pnrt_read_display")
+        return out
+
+    def display_ptr(self) -> int:
+        return int(self._lib.pnrt_display_device_ptr(self._ctx) or 0)
+
+    def luma_histogram(self, source="accum", band: int = 1, n_shards: int = 1, shard: int = 0,
+                       src_ptr: int | None = None) -> dict:
+        """The luminance histogram of a display source over the rows of a shard selector
+        (pnrt_luma_histogram_read; synchronous): ``n_pixels``, ``n_counted`` and ``bins``,
+        a (512,) int64 array, 16 bins per octave, luminance 1.0 in bin 256.  Histograms of
+        disjoint selectors add up (``merge_histograms``)."""
+        h = N.LumaHistogram()
+        self._ck(self._lib.pnrt_luma_histogram_read(self._ctx, self._enum("display source", N.DISPLAY_SOURCES, source),
+                                                    ctypes.c_void_p(src_ptr or 0), band, n_shards, shard, ctypes.byref(h)),
+                 "pnrt_luma_histogram_read")
+        return {"n_pixels": h.n_pixels, "n_counted": h.n_counted, "bins": np.array(h.bins, np.int64)}
+
     # ---- ray queries ---------------------------------------------------------------------
-    def query_rays(self, rays: np.ndarray, any_hit: bool = False) -> np.ndarray:
+    def query_rays(self,rays: np.ndarray, any_hit: bool = False) -> np.ndarray:
         """The closest hit (or, with ``any_hit``, whether anything is hit) of caller rays
         against the uploaded scene (pnrt_query_rays; synchronous): rays (n, 7) float32 =
         origin, direction, tMax -> (n, 16) uint32 records, see ``decode_hits``.  The
@@ -406,6 +451,30 @@ def merge_convergence(stats: list) -> dict:
     out["min_frames"] = min((s["min_frames"] for s in some), default=0)
     out["max_frames"] = max((s["max_frames"] for s in some), default=0)
     return _with_mean_error(out)
+
+
+def merge_histograms(hists: list) -> dict:
+    """The histogram of the union of disjoint row sets (``PathTracer.luma_histogram``
+    dicts): every field adds."""
+    return {"n_pixels": sum(h["n_pixels"] for h in hists), "n_counted": sum(h["n_counted"] for h in hists),
+            "bins": sum((np.asarray(h["bins"], np.int64) for h in hists), np.zeros(N.LUMA_BINS, np.int64))}
+
+
+def exposure_from_histogram(hist: dict, low: int = 50, high: int = 950, key: float = 0.18) -> float:
+    """The exposure that brings the histogram's trimmed mean bin -- the pixels between
+    the ``low`` and ``high`` permille of the counted ones -- to the luminance ``key``
+    (pnrt_exposure_from_histogram: host code, integer arithmetic, a 1/16-stop grid)."""
+    bins = np.asarray(hist["bins"], np.int64)
+    if bins.shape != (N.LUMA_BINS,):
+        raise ValueError(f"exposure_from_histogram: need {N.LUMA_BINS} bins, got {bins.shape}")
+    h = N.LumaHistogram(int(hist["n_pixels"]), int(hist["n_counted"]), (ctypes.c_int64 * N.LUMA_BINS)(*map(int, bins)))
+    out = ctypes.c_float()
+    rc = N.device_lib().pnrt_exposure_from_histogram(ctypes.byref(h), low, high, ctypes.c_float(key), ctypes.byref(out))
+    if rc != 0:
+        e = PnrtError(f"pnrt_exposure_from_histogram failed ({rc}): need 0 <= low < high <= 1000 and a finite key > 0")
+        e.code = rc
+        raise e
+    return out.value
 
 
 def shard_rows(height: int, band: int, n_shards: int, shard: int) -> np.ndarray:
