@@ -108,6 +108,65 @@ int pnrt_upload_scene(pnrt_ctx* ctx,
  * reference's redraw does (pnrt_reset_accum). */
 int pnrt_update_materials(pnrt_ctx* ctx, int first, int count, const float* materials18);
 
+/* In-place geometry edit.  Not in the reference, which places every model once
+ * with a matrix (main.cpp:207-237) and offers no edit of geometry; what it
+ * replaces here is a whole pnrt_upload_scene after a model was moved, scaled
+ * or deformed.  Overwrites vertex records first .. first + count - 1 with count
+ * records of 15 floats in the main.cpp:412-428 layout, world space, and brings
+ * every record derived from them (per-triangle positions and attributes, the
+ * light records) and every BVH box up to date on the device.  Tree topology,
+ * triangle order, material and texture ids, child refs and the leaf table do
+ * not change.  Synchronous: it waits for the calls in flight, which render
+ * with the old geometry, and returns when the scene is current.  The caller
+ * resets the accumulation as a redraw does (pnrt_reset_accum).  Nothing is
+ * allocated per call beyond a staging buffer that grows to the largest edit.
+ *
+ * The refit rule is Bound::Union (bound.hpp:4-28) with the comparisons
+ * min(x, y) = (y < x) ? y : x and max(x, y) = (x < y) ? y : x, so on a tie --
+ * -0 against +0 -- the EARLIER operand stays, and a NaN coordinate never
+ * enters a box:
+ *   non-empty leaf  the fold of its triangles in ascending order, vertices p0,
+ *                   p1, p2, starting from (FLT_MAX, lowest);
+ *   interior node   fold(left child's box, right child's box);
+ *   empty leaf      (start == end) keeps its uploaded box, which takes part in
+ *                   its parent's fold.
+ * With unchanged vertices this gives back BuildBVH's own boxes bit for bit.
+ * Positions are not validated (pnrt_upload_scene does not either): a box with
+ * a non-finite coordinate switches the traversal to PNRT_TRAVERSE_EXACT, as at
+ * upload.  A refit tree and a tree rebuilt for the new positions can render
+ * different image bits (a triangle is tested only when every box above it
+ * passes the slab test): the image is what ray_tracing.comp renders from the
+ * refit node array, which pnrt_read_bvh_boxes returns.
+ *
+ * lights: the set and order of light triangles cannot change, their areas can.
+ * NULL keeps the uploaded prefix areas and lights_sum_area -- the caller's
+ * statement that no emissive triangle changed area -- and lights_sum_area is
+ * then ignored; otherwise exactly the uploaded n_lights records of 3 floats
+ * with the same triangle index in every entry, and the prefix areas and
+ * lights_sum_area are taken as pnrt_upload_scene takes them.
+ *
+ * Afterwards the guide images are stale (pnrt_denoise* answer PNRT_E_STATE
+ * until pnrt_render_guides).  Errors: PNRT_E_STATE before pnrt_upload_scene;
+ * PNRT_E_ARG, with nothing changed, for a range outside the uploaded vertex
+ * array, NULL vertices with count > 0, a device pointer that is not 4-byte
+ * aligned, or a lights entry naming another triangle than the uploaded one
+ * (the message names the entry); PNRT_E_TRACE as pnrt_read_accum returns it.
+ * count == 0 with lights == NULL does nothing.  The _device form reads the
+ * records from device memory of the context's device. */
+int pnrt_update_vertices(pnrt_ctx* ctx, int first, int count, const float* vertices15,
+                         const float* lights, float lights_sum_area);
+int pnrt_update_vertices_device(pnrt_ctx* ctx, int first, int count, const void* vertices15_dev,
+                                const float* lights, float lights_sum_area);
+
+/* The boxes the device currently holds, into floats 0-5 of every node of the
+ * caller's pre-order node array (main.cpp:488-501 layout); floats 6-11 are
+ * read, not written.  Not in the reference.  The array must be the topology
+ * that was uploaded -- the library keeps no host copy of the scene --:
+ * PNRT_E_ARG, with nothing written, when its interior-node count or a child's
+ * kind (leaf or interior) disagrees with the uploaded tree.  An empty leaf's
+ * box comes back as uploaded.  Synchronous. */
+int pnrt_read_bvh_boxes(pnrt_ctx* ctx, float* bvh_nodes12, int n_nodes);
+
 /* Replaces the albedo texture uploads (main.cpp:527-554, units 5..24):
  * tightly packed 8-bit rows as stbi_load returns them; GL's default
  * UNPACK_ALIGNMENT of 4 is applied as glTexImage2D would. slot 0..19. */

@@ -11,6 +11,7 @@
  *                                              pnrt_bvh_build + pnrt_scene_set_bvh)
  *   light prefix list (main.cpp:374-383)       pnrt_scene_build
  *   packing loops (main.cpp:409-524)           pnrt_scene_pack
+ *   (none: models are placed once)             pnrt_bvh_refit_cpu, pnrt_scene_relight
  *   Camera::UpdateCamera (camera.hpp:11-31)    pnrt_camera_update, pnrt_camera_state_init
  *   Camera::UpdateRotate/TranslateUV/Fov       pnrt_camera_rotate/_translate/_zoom
  *     (camera.hpp:33-65, main.cpp:118-142)
@@ -77,6 +78,28 @@ int pnrt_scene_set_bvh(pnrt_scene* s, const int32_t* order, const float* bvh_nod
  * context): the CPU counterpart the GPU build is checked against. */
 int pnrt_bvh_build_cpu(const float* tri_bounds9, int n_triangles, float* nodes_out, int node_capacity,
                        int* n_nodes_out, int32_t* order_out, int* max_depth_out);
+/* After a geometry edit (libpnrt.so pnrt_update_vertices; not in the reference,
+ * which never moves a model): bare-array functions on the main.cpp-layout
+ * arrays, as pnrt_bvh_build_cpu.
+ * pnrt_bvh_refit_cpu: the CPU counterpart of the device refit.  Floats 0-5 of
+ * every node of the pre-order array are recomputed bottom-up for the vertices
+ * given, topology unchanged, with Bound::Union (bound.hpp:4-28) and this
+ * library's min/max, (y < x) ? y : x and (x < y) ? y : x -- on a tie the earlier
+ * operand stays: a non-empty leaf is the fold of its triangles in ascending
+ * order, vertices p0, p1, p2, from (FLT_MAX, lowest); an interior node is
+ * fold(left box, right box); an empty leaf (start == end) keeps its box.  With
+ * unchanged vertices BuildBVH's own boxes come back bit for bit. */
+int pnrt_bvh_refit_cpu(const float* vertices15, int n_vertices, const float* triangles6, int n_triangles,
+                       float* bvh_nodes12, int n_nodes);
+/* pnrt_scene_relight: float 5 of every triangle record (its area) recomputed as
+ * pnrt_scene_add_mesh does, (float)((double)length(cross(p1-p0, p2-p0)) * 0.5),
+ * and the light list rebuilt as pnrt_scene_build does (main.cpp:374-383) into
+ * lights3_out (3 floats each, at most n_lights_capacity entries; NULL with
+ * capacity 0 only counts); *sum_area = the last prefix, 0 without lights
+ * (main.cpp:392). */
+int pnrt_scene_relight(const float* vertices15, int n_vertices, float* triangles6, int n_triangles,
+                       const float* materials18, int n_materials, float* lights3_out, int n_lights_capacity,
+                       int* n_lights, float* sum_area);
 typedef struct {
     int n_vertices, n_materials, n_triangles, n_nodes, n_lights;
     float lights_sum_area;

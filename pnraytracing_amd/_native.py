@@ -182,6 +182,8 @@ def _type_host(lib):
     _sig(lib, "pnrt_scene_tri_bounds", INT, P, F)
     _sig(lib, "pnrt_scene_set_bvh", INT, P, I32, F, INT, INT)
     _sig(lib, "pnrt_bvh_build_cpu", INT, F, INT, F, INT, PINT, I32, PINT)
+    _sig(lib, "pnrt_bvh_refit_cpu", INT, F, INT, F, INT, F, INT)
+    _sig(lib, "pnrt_scene_relight", INT, F, INT, F, INT, F, INT, F, INT, PINT, ctypes.POINTER(ctypes.c_float))
     _sig(lib, "pnrt_camera_update", INT, F, F, F, ctypes.c_float, ctypes.c_float, F)
     _sig(lib, "pnrt_camera_pixel_ray", INT, F, INT, INT, INT, INT, F)
     _sig(lib, "pnrt_hdr_decode_rgbe", INT, U8, ctypes.c_int64, PINT, PINT, F)
@@ -202,6 +204,9 @@ def _type_device(lib):
     _sig(lib, "pnrt_upload_scene", INT, P, F, INT, F, INT, F, INT, F, INT, F, INT, ctypes.c_float)
     _sig(lib, "pnrt_upload_texture", INT, P, INT, U8, INT, INT, INT)
     _sig(lib, "pnrt_update_materials", INT, P, INT, INT, F)
+    _sig(lib, "pnrt_update_vertices", INT, P, INT, INT, F, F, ctypes.c_float)
+    _sig(lib, "pnrt_update_vertices_device", INT, P, INT, INT, P, F, ctypes.c_float)
+    _sig(lib, "pnrt_read_bvh_boxes", INT, P, F, INT)
     _sig(lib, "pnrt_upload_env", INT, P, F, F, INT, INT)
     _sig(lib, "pnrt_set_frame", INT, P, INT, INT, ctypes.POINTER(Camera), INT)
     _sig(lib, "pnrt_set_options", INT, P, INT)

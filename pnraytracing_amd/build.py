@@ -28,7 +28,7 @@ ARCH = os.environ.get("PNRT_OFFLOAD_ARCH", "gfx950")
 DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
                "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pt_adaptive.h", "pt_query.h", "pn_math.h",
-               "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h", "pt_display.h"]
+               "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h", "pt_display.h", "pt_refit.h"]
 
 
 def _run(cmd, cwd=None):
@@ -174,6 +174,20 @@ def build_abi_caller(force=False):
     return out
 
 
+def build_refit_abi_caller(force=False):
+    """tests/abi/c_abi_refit: an in-place geometry edit (pnrt_update_vertices,
+    pnrt_read_bvh_boxes) from a C translation unit (TEST-ONLY; tests/test_gpu_refit_c_abi.py)."""
+    src = os.path.join(REPO, "tests", "abi", "c_abi_refit.c")
+    out = os.path.join(REPO, "tests", "abi", "c_abi_refit")
+    deps = [src, os.path.join(INC, "pnrt.h"), os.path.join(PKG, "libpnrt.so")]
+    if not all(os.path.exists(d) for d in deps):
+        return None
+    if force or _stale(out, deps):
+        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, src, "-o", out, "-L", PKG, "-lpnrt",
+              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return out
+
+
 def build_oracle(force=False):
     odir = os.path.join(REPO, "oracle")
     _run(["make", "-s", "-C", odir] + (["-B"] if force else []))
@@ -187,6 +201,7 @@ def build_all(force=False):
     build_device(force)
     build_diag_variants(force)
     build_abi_caller(force)
+    build_refit_abi_caller(force)
     build_oracle(force)
 
 

@@ -422,6 +422,81 @@ int pnrt_bvh_build_cpu(const float* tb, int n, float* nodes_out, int cap, int* n
     return 0;
 }
 
+// The CPU counterpart of libpnrt.so's refit (pnrt_update_vertices): pre-order ids
+// put every child after its parent, so one descending pass is bottom-up.
+int pnrt_bvh_refit_cpu(const float* V, int nv, const float* T, int nt, float* nb, int nn) {
+    if (!V || !T || !nb || nv <= 0 || nt <= 0 || nn <= 0) return fail(-1, "bvh_refit_cpu: bad arguments");
+    for (int i = 0; i < nt; ++i)
+        for (int k = 0; k < 3; ++k) {
+            const int id = (int)T[6 * (size_t)i + k];
+            if (id < 0 || id >= nv) return fail(-2, "bvh_refit_cpu: triangle " + std::to_string(i) + " has an out-of-range vertex index");
+        }
+    for (int i = 0; i < nn; ++i) {
+        const float* q = nb + 12 * (size_t)i;
+        const int rc = (int)q[7], s0 = (int)q[8], e0 = (int)q[9];
+        if (rc == -1 ? (s0 < 0 || e0 > nt || s0 > e0) : (rc <= i + 1 || rc >= nn))
+            return fail(-3, "bvh_refit_cpu: node " + std::to_string(i) + " is inconsistent");
+    }
+    auto load = [&](int i) {
+        Bound b;
+        const float* q = nb + 12 * (size_t)i;
+        b.pMin = vec3(q[0], q[1], q[2]); b.pMax = vec3(q[3], q[4], q[5]);
+        return b;
+    };
+    for (int i = nn - 1; i >= 0; --i) {
+        float* q = nb + 12 * (size_t)i;
+        const int rc = (int)q[7], s0 = (int)q[8], e0 = (int)q[9];
+        Bound b;
+        if (rc == -1) {
+            if (s0 == e0) continue;               // an empty leaf keeps its box
+            for (int t = s0; t < e0; ++t)
+                for (int k = 0; k < 3; ++k) {
+                    const float* p = V + 15 * (size_t)(int)T[6 * (size_t)t + k];
+                    b.Union(vec3(p[0], p[1], p[2]));
+                }
+        } else {
+            b = load(i + 1);
+            b.Union(load(rc));
+        }
+        q[0] = b.pMin.x; q[1] = b.pMin.y; q[2] = b.pMin.z;
+        q[3] = b.pMax.x; q[4] = b.pMax.y; q[5] = b.pMax.z;
+    }
+    return 0;
+}
+
+// Areas as ModelOutput computes them, the light list as build_lights does.
+int pnrt_scene_relight(const float* V, int nv, float* T, int nt, const float* M, int nm, float* lights_out, int cap,
+                       int* n_lights_out, float* sum_area_out) {
+    if (!V || !T || !M || nv <= 0 || nt <= 0 || nm <= 0 || cap < 0 || (cap > 0 && !lights_out))
+        return fail(-1, "scene_relight: bad arguments");
+    for (int i = 0; i < nt; ++i) {
+        const float* t = T + 6 * (size_t)i;
+        for (int k = 0; k < 3; ++k)
+            if ((int)t[k] < 0 || (int)t[k] >= nv)
+                return fail(-2, "scene_relight: triangle " + std::to_string(i) + " has an out-of-range vertex index");
+        if ((int)t[3] < 0 || (int)t[3] >= nm)
+            return fail(-3, "scene_relight: triangle " + std::to_string(i) + " references an unknown material");
+    }
+    int n = 0;
+    float prefix = 0.f;
+    for (int i = 0; i < nt; ++i) {
+        float* t = T + 6 * (size_t)i;
+        auto pos = [&](int k) { const float* p = V + 15 * (size_t)(int)t[k]; return vec3(p[0], p[1], p[2]); };
+        const vec3 p0 = pos(0), p1 = pos(1), p2 = pos(2);
+        t[5] = (float)((double)length(cross(p1 - p0, p2 - p0)) * 0.5);
+        const float* m = M + 18 * (size_t)(int)t[3];
+        if (!(m[0] == 0.f && m[1] == 0.f && m[2] == 0.f)) {
+            prefix = n ? t[5] + prefix : t[5];    // main.cpp:374-383: this area += the previous prefix
+            if (n < cap) { lights_out[3 * (size_t)n] = (float)i; lights_out[3 * (size_t)n + 1] = prefix; lights_out[3 * (size_t)n + 2] = 0.f; }
+            ++n;
+        }
+    }
+    if (n_lights_out) *n_lights_out = n;
+    if (sum_area_out) *sum_area_out = n ? prefix : 0.f;
+    if (n > cap && lights_out) return fail(-4, "scene_relight: " + std::to_string(n) + " lights exceed the capacity");
+    return 0;
+}
+
 int pnrt_scene_set_bvh(pnrt_scene* s, const int32_t* order, const float* nb, int n_nodes, int max_depth) {
     if (int rc = check_buildable(s, "set_bvh")) return rc;
     const int n = (int)s->triangles.size();

@@ -28,6 +28,7 @@
 #include "pt_query.h"
 #include "pt_reproject.h"
 #include "pt_display.h"
+#include "pt_refit.h"
 
 __global__ void pt_pack_rows_kernel(const float4* accum, float4* dst, int width, int rows, int band,
                                     int n_shards, int shard) {
@@ -95,6 +96,8 @@ struct pnrt_ctx {
     std::vector<int> light_mat;            // material of each light record's triangle (pnrt_update_materials)
     std::vector<float4> light_rec_host;    // host copy of the light records (patched, then one upload)
     std::vector<float> mat_emit;           // host copy of every material's emission (3 floats each)
+    std::vector<int> light_tri;            // triangle of each uploaded light entry (pnrt_update_vertices checks them)
+    std::vector<int> level_off;            // interior nodes of tree level d are indices level_off[d] .. level_off[d + 1] - 1
     float env_max = 0.f;                   // largest |texel| component of the env image (NaN: a NaN texel)
     // env + textures
     void* hdr = nullptr;
@@ -214,6 +217,9 @@ struct pnrt_ctx {
     uint32_t* disp = nullptr;              // the RGBA8 display image
     int disp_width = 0, disp_height = 0;   // its size (0: none yet)
     LumaHist* luma_hist = nullptr;         // pnrt_luma_histogram_read's device record
+    // in-place geometry edits (pnrt_update_vertices; pt_refit.h): none until the first call
+    float* rf_stage = nullptr;             size_t rf_stage_cap = 0;    // the host form's staging buffer: vertex records in
+    RefitResult* rf_res = nullptr;         // the root box and the non-finite flag the host reads back
 };
 
 static int set_err(pnrt_ctx* c, int code, const std::string& m) {
@@ -1182,6 +1188,7 @@ void pnrt_destroy(pnrt_ctx* c) {
     (void)hipFree(c->rp_pos); (void)hipFree(c->rp_nrm); (void)hipFree(c->rp_acc); (void)hipFree(c->rp_mom);
     (void)hipFree(c->rp_counts);
     (void)hipFree(c->disp); (void)hipFree(c->luma_hist);
+    (void)hipFree(c->rf_stage); (void)hipFree(c->rf_res);
 
     for (auto& p : c->ev_pending) { c->ev_pool.push_back(p.second.first); c->ev_pool.push_back(p.second.second); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1242,6 +1249,19 @@ static void set_emit_max(pnrt_ctx* c) {
         m = (std::isnan(e) || std::isnan(m)) ? std::numeric_limits<float>::quiet_NaN() : std::max(m, e);
     }
     c->scene.emit_max = m;
+}
+
+// The light list's prefix areas as the kernels take them (pnrt_upload_scene,
+// pnrt_update_vertices): lights_sum_area, and the kernel-argument copy of a short list.
+// GetLightIndex is a lower bound: a linear scan returns the same index iff the
+// prefix areas are non-decreasing (they are for main.cpp:374-383's list)
+static void set_light_areas(DevScene& s, const std::vector<float2>& lights, int nl, float lsum) {
+    s.lights_sum_area = lsum;
+    bool mono = nl <= WF_LIGHT_SCAN;
+    for (int k = 1; mono && k < nl; ++k) mono = lights[k].y >= lights[k - 1].y;
+    for (int k = 0; mono && k < nl; ++k) mono = lights[k].y == lights[k].y;
+    s.light_scan = mono ? 1 : 0;
+    for (int k = 0; k < WF_LIGHT_SCAN; ++k) s.lscan[k] = k < nl ? lights[k].y : 0.f;
 }
 
 int pnrt_upload_scene(pnrt_ctx* c, const float* V, int nv, const float* M, int nm, const float* T, int nt,
@@ -1329,10 +1349,12 @@ int pnrt_upload_scene(pnrt_ctx* c, const float* V, int nv, const float* M, int n
     // (the top levels share cache lines); the visit order is
     // carried by the child refs and the axis, not by the numbering
     order.clear();
+    std::vector<int> level_off;              // depth is non-decreasing along the order: one index range per level
     if (fint(N[7]) != -1) order.push_back(0);
     for (size_t q = 0; q < order.size(); ++q) {
         const int i = order[q];
         dn[i] = (int)q;
+        if (depth[i] == (int)level_off.size()) level_off.push_back((int)q);
         const float* n = N + 12 * (size_t)i;
         const int rc = fint(n[7]);
         if (fint(N[12 * (size_t)(i + 1) + 7]) != -1) order.push_back(i + 1);
@@ -1378,10 +1400,12 @@ int pnrt_upload_scene(pnrt_ctx* c, const float* V, int nv, const float* M, int n
     // trace-kernel stack bound: at most one deferred sibling per BVH level
     c->wf_stack_need = maxd + 2;
     std::vector<float2> lights(nl > WF_LIGHT_SCAN ? nl : WF_LIGHT_SCAN, make_float2(0.f, 0.f));
+    std::vector<int> light_tri(nl);
     for (int i = 0; i < nl; ++i) {
         lights[i] = make_float2(Lt[3 * (size_t)i], Lt[3 * (size_t)i + 1]);
         int li = fint(Lt[3 * (size_t)i]);
         if (li < 0 || li >= nt) return set_err(c, PNRT_E_SCENE, "light references an out-of-range triangle");
+        light_tri[i] = li;
     }
     std::vector<float> mats(M, M + 18 * (size_t)nm);
     // light records: what TriangleSample (:598-624) and the emission (:887) read for
@@ -1427,7 +1451,6 @@ int pnrt_upload_scene(pnrt_ctx* c, const float* V, int nv, const float* M, int n
         (rc = upload(c, std::vector<float4>(1, make_float4(0.f, 0.f, 0.f, 0.f)), &s.zero4)))
         return rc;
     s.n_nodes = (int)order.size(); s.n_tris = nt; s.n_verts = nv; s.n_materials = nm; s.n_lights = nl;
-    s.lights_sum_area = lsum;
     const float* root = N;
     for (int k = 0; k < 3; ++k) { s.root_min[k] = root[k]; s.root_max[k] = root[3 + k]; }
     // z-slab culling's proof needs finite boxes (then a culling-enabled ray's
@@ -1440,14 +1463,10 @@ int pnrt_upload_scene(pnrt_ctx* c, const float* V, int nv, const float* M, int n
     s.root_ref = root_ref;
     s.has_leaf_table = has_leaf_table;
     s.n_leaf_table = (int)leaf_table.size();
-    {   // GetLightIndex is a lower bound: a linear scan returns the same index iff the
-        // prefix areas are non-decreasing (they are for main.cpp:374-383's list)
-        bool mono = nl <= WF_LIGHT_SCAN;
-        for (int k = 1; mono && k < nl; ++k) mono = lights[k].y >= lights[k - 1].y;
-        for (int k = 0; mono && k < nl; ++k) mono = lights[k].y == lights[k].y;
-        s.light_scan = mono ? 1 : 0;
-        for (int k = 0; k < WF_LIGHT_SCAN; ++k) s.lscan[k] = k < nl ? lights[k].y : 0.f;
-    }
+    set_light_areas(s, lights, nl, lsum);
+    c->light_tri = light_tri;
+    level_off.push_back((int)order.size());
+    c->level_off = level_off;
     c->mat_emit.resize(3 * (size_t)nm);
     for (int m = 0; m < nm; ++m)
         for (int k = 0; k < 3; ++k) c->mat_emit[3 * (size_t)m + k] = M[18 * (size_t)m + k];
@@ -1492,6 +1511,143 @@ int pnrt_update_materials(pnrt_ctx* c, int first, int count, const float* rec) {
     set_emit_max(c);
     ++c->scene_epoch;                    // primary records hold the hit material's emission
     return PNRT_OK;
+}
+
+#ifndef REFIT_MAX_STAGE
+#define REFIT_MAX_STAGE (1 << 20)    // vertex records per staged copy of the host form (60 MB)
+#endif
+
+// pnrt_update_vertices / _device: `src_host` or `src_dev` holds the records (pt_refit.h)
+static int update_vertices(pnrt_ctx* c, const char* who, int first, int count, const float* src_host, const float* src_dev,
+                           const float* Lt, float lsum) {
+    if (!c) return PNRT_E_ARG;
+    if (!c->has_scene) return set_err(c, PNRT_E_STATE, std::string(who) + ": upload_scene first");
+    DevScene& s = c->scene;
+    if (first < 0 || count < 0 || first > s.n_verts - count)
+        return set_err(c, PNRT_E_ARG, std::string(who) + ": vertex range outside the uploaded array");
+    if (count > 0 && !src_host && !src_dev) return set_err(c, PNRT_E_ARG, std::string(who) + ": vertices is NULL");
+    if ((uintptr_t)src_dev & 3u) return set_err(c, PNRT_E_ARG, std::string(who) + ": vertices must be 4-byte aligned");
+    if (count == 0 && !Lt) return PNRT_OK;
+    const int nl = s.n_lights;
+    std::vector<float2> lights;
+    if (Lt) {
+        lights.assign(nl > WF_LIGHT_SCAN ? nl : WF_LIGHT_SCAN, make_float2(0.f, 0.f));
+        for (int i = 0; i < nl; ++i) {
+            if (fint(Lt[3 * (size_t)i]) != c->light_tri[i])
+                return set_err(c, PNRT_E_ARG, std::string(who) + ": lights entry " + std::to_string(i) + " names triangle " +
+                                                  std::to_string(fint(Lt[3 * (size_t)i])) + ", the uploaded one " +
+                                                  std::to_string(c->light_tri[i]) + " (the light list cannot change)");
+            lights[i] = make_float2(Lt[3 * (size_t)i], Lt[3 * (size_t)i + 1]);
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // the calls in flight render with the old geometry
+    HIPCHK(c, sync_all(c));
+    if (count > 0) {
+        int rc;
+        if (!c->rf_res) HIPCHK(c, hipMalloc(&c->rf_res, sizeof(RefitResult)));
+        if (src_host && (rc = grow(c, (void**)&c->rf_stage, &c->rf_stage_cap, (size_t)std::min(count, REFIT_MAX_STAGE) * 60)))
+            return rc;
+        hipStream_t st = c->stream;
+        RefitResult res0{};
+        for (int k = 0; k < 3; ++k) { res0.root[k] = s.root_min[k]; res0.root[3 + k] = s.root_max[k]; }
+        HIPCHK(c, hipMemcpyAsync(c->rf_res, &res0, sizeof res0, hipMemcpyHostToDevice, st));
+        float4* verts = const_cast<float4*>(s.verts);
+        float4* nodes = const_cast<float4*>(s.nodes);
+        if (src_dev)
+            hipLaunchKernelGGL(pt_refit_scatter_kernel, dim3((count + 255) / 256), dim3(256), 0, st, src_dev, verts, first, count,
+                               s.n_verts);
+        else
+            for (int at = 0; at < count; at += REFIT_MAX_STAGE) {
+                const int m = std::min(count - at, REFIT_MAX_STAGE);
+                // (a pageable copy: the staging buffer is free again when it returns)
+                HIPCHK(c, hipMemcpyAsync(c->rf_stage, src_host + 15 * (size_t)at, (size_t)m * 60, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(pt_refit_scatter_kernel, dim3((m + 255) / 256), dim3(256), 0, st, c->rf_stage, verts, first + at, m,
+                                   s.n_verts);
+                HIPCHK(c, hipStreamSynchronize(st));
+            }
+        hipLaunchKernelGGL(pt_refit_gather_kernel, dim3((s.n_tris + 255) / 256), dim3(256), 0, st, s.tri_idx, s.verts,
+                           const_cast<float4*>(s.tris), const_cast<float4*>(s.tri_attr), s.n_tris, s.n_verts);
+        hipLaunchKernelGGL(pt_refit_lights_kernel, dim3((nl + 1 + 255) / 256), dim3(256), 0, st, s.lights, s.tri_idx, s.verts,
+                           const_cast<float4*>(s.light_rec), nl, s.n_tris, s.n_verts);
+        const int nn = s.n_nodes;
+        hipLaunchKernelGGL(pt_refit_leaves_kernel, dim3(nn ? (2 * (unsigned)nn + 255) / 256 : 1), dim3(256), 0, st, nodes, nn,
+                           s.tris, s.n_tris, s.leaf_table, s.n_leaf_table, s.has_leaf_table, s.root_ref, c->rf_res);
+        // the deepest level has leaf children only; level 0 is the root's launch
+        const int levels = (int)c->level_off.size() - 1;
+        for (int d = levels - 2; d >= 1; --d) {
+            const int lo = c->level_off[d], hi = c->level_off[d + 1];
+            hipLaunchKernelGGL(pt_refit_level_kernel, dim3((2 * (unsigned)(hi - lo) + 255) / 256), dim3(256), 0, st, nodes, nn, lo,
+                               hi, 0, c->rf_res);
+        }
+        if (nn > 0) hipLaunchKernelGGL(pt_refit_level_kernel, dim3(1), dim3(64), 0, st, nodes, nn, 0, 1, 1, c->rf_res);
+        HIPCHK(c, hipGetLastError());
+        RefitResult res{};
+        HIPCHK(c, hipMemcpyAsync(&res, c->rf_res, sizeof res, hipMemcpyDeviceToHost, st));
+        // pnrt_update_materials patches the host copy of the light records and uploads spans of it
+        HIPCHK(c, hipMemcpyAsync(c->light_rec_host.data(), s.light_rec, c->light_rec_host.size() * sizeof(float4),
+                                 hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        for (int k = 0; k < 3; ++k) { s.root_min[k] = res.root[k]; s.root_max[k] = res.root[3 + k]; }
+        c->boxes_finite = res.nonfinite == 0;
+    }
+    if (Lt) {
+        HIPCHK(c, hipMemcpy(const_cast<float2*>(s.lights), lights.data(), lights.size() * sizeof(float2), hipMemcpyHostToDevice));
+        set_light_areas(s, lights, nl, lsum);
+    }
+    ++c->scene_epoch;                    // primary records, guide images: traced through the old geometry
+    return check_fault(c);
+}
+
+int pnrt_update_vertices(pnrt_ctx* c, int first, int count, const float* v, const float* lights, float lsum) {
+    return update_vertices(c, "update_vertices", first, count, v, nullptr, lights, lsum);
+}
+
+int pnrt_update_vertices_device(pnrt_ctx* c, int first, int count, const void* v, const float* lights, float lsum) {
+    return update_vertices(c, "update_vertices_device", first, count, nullptr, static_cast<const float*>(v), lights, lsum);
+}
+
+int pnrt_read_bvh_boxes(pnrt_ctx* c, float* N, int nn) {
+    if (!c) return PNRT_E_ARG;
+    if (!c->has_scene) return set_err(c, PNRT_E_STATE, "read_bvh_boxes: upload_scene first");
+    if (!N || nn <= 0) return set_err(c, PNRT_E_ARG, "read_bvh_boxes: no node array");
+    // the upload's breadth-first numbering, recovered from the caller's pre-order array
+    std::vector<int> order;
+    if (fint(N[7]) != -1) order.push_back(0);
+    for (size_t q = 0; q < order.size(); ++q) {
+        const int i = order[q];
+        const int rc = fint(N[12 * (size_t)i + 7]);
+        if (order.size() > (size_t)c->n_interior)
+            return set_err(c, PNRT_E_ARG, "read_bvh_boxes: the node array has more interior nodes than the uploaded tree's " +
+                                              std::to_string(c->n_interior));
+        if (i + 1 >= nn || rc <= 0 || rc >= nn)
+            return set_err(c, PNRT_E_ARG, "read_bvh_boxes: the node array is not the uploaded tree");
+        if (fint(N[12 * (size_t)(i + 1) + 7]) != -1) order.push_back(i + 1);
+        if (fint(N[12 * (size_t)rc + 7]) != -1) order.push_back(rc);
+    }
+    if ((int)order.size() != c->n_interior)
+        return set_err(c, PNRT_E_ARG, "read_bvh_boxes: the node array has " + std::to_string(order.size()) +
+                                          " interior nodes, the uploaded tree " + std::to_string(c->n_interior));
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_all(c));
+    std::vector<float> dev(order.size() * 16);
+    if (!dev.empty()) HIPCHK(c, hipMemcpy(dev.data(), c->scene.nodes, dev.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < order.size(); ++k) {
+        const int ch[2] = {order[k] + 1, fint(N[12 * (size_t)order[k] + 7])};
+        for (int side = 0; side < 2; ++side) {
+            uint32_t ref;
+            std::memcpy(&ref, &dev[16 * k + 12 + side], 4);
+            if (((ref & REF_LEAF) != 0) != (fint(N[12 * (size_t)ch[side] + 7]) == -1))
+                return set_err(c, PNRT_E_ARG, "read_bvh_boxes: node " + std::to_string(ch[side]) +
+                                                  " is a leaf in one tree and interior in the other");
+        }
+    }
+    for (size_t k = 0; k < order.size(); ++k) {
+        const int ch[2] = {order[k] + 1, fint(N[12 * (size_t)order[k] + 7])};
+        for (int side = 0; side < 2; ++side) std::memcpy(N + 12 * (size_t)ch[side], &dev[16 * k + 6 * side], 24);
+    }
+    for (int k = 0; k < 3; ++k) { N[k] = c->scene.root_min[k]; N[3 + k] = c->scene.root_max[k]; }
+    return check_fault(c);
 }
 
 int pnrt_upload_texture(pnrt_ctx* c, int slot, const uint8_t* px, int w, int h, int ch) {

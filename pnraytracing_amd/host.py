@@ -220,6 +220,56 @@ class PackedScene:
         return self.vertices, self.materials, self.triangles, self.nodes, self.lights
 
 
+def bvh_refit_cpu(vertices: np.ndarray, triangles: np.ndarray, nodes: np.ndarray) -> np.ndarray:
+    """A copy of the (nn, 12) pre-order node array with every box refit bottom-up for
+    ``vertices``, topology unchanged (pnrt_bvh_refit_cpu): the CPU counterpart of
+    ``PathTracer.update_vertices``'s refit, the same rule."""
+    V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 15)
+    T = np.ascontiguousarray(triangles, np.float32).reshape(-1, 6)
+    out = np.array(nodes, np.float32, order="C").reshape(-1, 12)
+    _check(N.host_lib().pnrt_bvh_refit_cpu(N.fptr(V), len(V), N.fptr(T), len(T), N.fptr(out), len(out)), "bvh_refit_cpu")
+    return out
+
+
+def scene_relight(vertices: np.ndarray, triangles: np.ndarray, materials: np.ndarray):
+    """(triangles with float 5 = the area for ``vertices``, lights (nl, 3), lights_sum_area):
+    areas as ModelOutput computes them, the list as main.cpp:374-383 (pnrt_scene_relight)."""
+    V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 15)
+    T = np.array(triangles, np.float32, order="C").reshape(-1, 6)
+    M = np.ascontiguousarray(materials, np.float32).reshape(-1, 18)
+    L = np.zeros((len(T), 3), np.float32)
+    nl, sa = ctypes.c_int(), ctypes.c_float()
+    _check(N.host_lib().pnrt_scene_relight(N.fptr(V), len(V), N.fptr(T), len(T), N.fptr(M), len(M), N.fptr(L), len(L),
+                                           ctypes.byref(nl), ctypes.byref(sa)), "scene_relight")
+    return T, L[:nl.value].copy(), float(sa.value)
+
+
+def refit_packed(packed: "PackedScene", first: int, vertices: np.ndarray) -> "PackedScene":
+    """The packed scene after ``PathTracer.update_vertices(first, vertices, lights=...)``: a
+    new :class:`PackedScene` with the records replaced, areas and lights from
+    pnrt_scene_relight and the nodes from pnrt_bvh_refit_cpu -- what an oracle of the
+    edited scene is built from, and where the call's ``lights`` come from."""
+    rec = np.ascontiguousarray(vertices, np.float32).reshape(-1, 15)
+    if first < 0 or first + len(rec) > len(packed.vertices):
+        raise ValueError(f"refit_packed: vertices {first} .. {first + len(rec)} are outside the {len(packed.vertices)} packed")
+    V = np.array(packed.vertices, np.float32, order="C")
+    V[first:first + len(rec)] = rec
+    T, L, sa = scene_relight(V, packed.triangles, packed.materials)
+    if not np.array_equal(L[:, 0], np.asarray(packed.lights, np.float32).reshape(-1, 3)[:, 0]):
+        raise ValueError("refit_packed: the edit changes which triangles are lights")
+    return dataclasses.replace(packed, vertices=V, triangles=T, lights=L, lights_sum_area=sa,
+                               nodes=bvh_refit_cpu(V, T, packed.nodes), tri_bounds=None)
+
+
+def model_vertices(meshes: "Mesh | Sequence[Mesh]", ops) -> np.ndarray:
+    """The (nv, 15) world-space vertex records of a model under the matrix ``ops``, through
+    the library's own ModelOutput code (a throw-away scene): what
+    ``PathTracer.update_vertices(first_vertex_of_the_model, ...)`` takes to move it."""
+    sb = SceneBuilder()
+    sb.add_model(meshes, ops, Material())
+    return sb.build().vertices
+
+
 class SceneBuilder:
     """Model list -> ModelOutput -> BuildBVH -> light list -> packed arrays."""
 

@@ -173,6 +173,14 @@ class InteractiveSession:
         self.frame_count += n
         return stats
 
+    def edit_vertices(self, first: int, vertices, lights=None, lights_sum_area=None):
+        """A model was moved, scaled or deformed: overwrite its vertex records and refit the
+        BVH in place (``PathTracer.update_vertices``, whose arguments these are), then the
+        depth-1 redraw frame of main.cpp:592-596, as any other edit of the scene is shown.
+        Returns ``frame(True)``'s result."""
+        self.pt.update_vertices(first, vertices, lights=lights, lights_sum_area=lights_sum_area)
+        return self.frame(True)
+
     def pick(self, px: int, py: int) -> dict:
         """What is under pixel (px, py) -- row 0 = bottom, as ``PathTracer.read_aov`` --: the
         decoded record (``tracer.decode_hits``, one ray: scalars and vectors) of the closest

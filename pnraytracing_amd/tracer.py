@@ -78,6 +78,46 @@ class PathTracer:
         rec = np.ascontiguousarray(records, np.float32).reshape(-1, 18)
         self._ck(self._lib.pnrt_update_materials(self._ctx, first, len(rec), N.fptr(rec)), "pnrt_update_materials")
 
+    @staticmethod
+    def _lights_args(lights, lights_sum_area):
+        if lights is None:
+            return None, None, ctypes.c_float(0.0)
+        L = np.ascontiguousarray(lights, np.float32).reshape(-1, 3)
+        if lights_sum_area is None:          # main.cpp:392: the last prefix area
+            lights_sum_area = float(L[-1, 1]) if len(L) else 0.0
+        # (an empty list still has to say "recompute": a non-NULL pointer nobody reads)
+        keep = L if len(L) else np.zeros((1, 3), np.float32)
+        return keep, N.fptr(keep), ctypes.c_float(lights_sum_area)
+
+    def update_vertices(self, first: int, vertices: np.ndarray, lights: np.ndarray | None = None,
+                        lights_sum_area: float | None = None):
+        """Overwrite vertex records first.. with (n, 15) world-space records in place and
+        refit the BVH boxes on the device (pnrt_update_vertices; synchronous): the tree's
+        topology stays, every box follows the new positions.  ``lights`` None keeps the
+        light list's prefix areas (no emissive triangle changed area); otherwise the
+        uploaded list with new areas ((n_lights, 3), the same triangle indices; see
+        ``host.refit_packed``), ``lights_sum_area`` defaulting to its last prefix.  Reset
+        the accumulation afterwards, as a redraw does."""
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 15)
+        keep, lp, ls = self._lights_args(lights, lights_sum_area)
+        self._ck(self._lib.pnrt_update_vertices(self._ctx, first, len(v), N.fptr(v) if len(v) else None, lp, ls),
+                 "pnrt_update_vertices")
+
+    def update_vertices_device(self, first: int, count: int, ptr: int, lights: np.ndarray | None = None,
+                               lights_sum_area: float | None = None):
+        """The same from device memory (pnrt_update_vertices_device): ``ptr`` holds ``count``
+        records of 15 floats, 4-byte aligned, on the context's device."""
+        keep, lp, ls = self._lights_args(lights, lights_sum_area)
+        self._ck(self._lib.pnrt_update_vertices_device(self._ctx, first, count, ctypes.c_void_p(ptr or 0), lp, ls),
+                 "pnrt_update_vertices_device")
+
+    def read_bvh_boxes(self, nodes: np.ndarray) -> np.ndarray:
+        """A copy of ``nodes`` -- the (nn, 12) pre-order node array that was uploaded -- with
+        floats 0-5 of every node replaced by the box the device holds (pnrt_read_bvh_boxes)."""
+        out = np.array(nodes, np.float32, order="C").reshape(-1, 12)
+        self._ck(self._lib.pnrt_read_bvh_boxes(self._ctx, N.fptr(out), len(out)), "pnrt_read_bvh_boxes")
+        return out
+
     def upload_texture(self, slot: int, pixels: np.ndarray, width: int, height: int, channels: int):
         px = np.ascontiguousarray(pixels, np.uint8).reshape(-1)
         self._ck(self._lib.pnrt_upload_texture(self._ctx, slot, N.u8ptr(px), width, height, channels),
