@@ -233,6 +233,49 @@ int pnrt_render(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames, int band
 int pnrt_batch_plan(pnrt_ctx* ctx, uint32_t n_frames, int band_rows, int n_shards, int shard,
                     uint32_t* frames_per_batch, uint32_t* n_batches, int64_t* batch_bytes);
 
+/* Per-frame cameras (not in the reference, whose camera ray goes through the same
+ * point of the pixel in every frame, ray_tracing.comp:980): frame first_frame + k is
+ * rendered as pnrt_render would render it if cameras[k] were the camera of
+ * pnrt_set_frame -- the camera ray, the miss colour of its direction, V at bounce 0
+ * and everything downstream.  The seed, the Sobol index, the blend weight
+ * 1 / (float)(frame + 1), the clamp, the frame order, the shard selector and the
+ * traversal mode are pnrt_render's, so the accumulation is the reference's shader
+ * run once per frame with that frame's camera uniforms.  A sub-pixel shift of
+ * lower_left per frame gives a box pixel filter; an eye moved over a lens disc with
+ * the image plane held at the focus distance a thin lens; an eye moved along a path
+ * camera motion blur (pnrt_camera_sequence, pnrt_host.h, makes the first two).
+ *
+ * Frame size and depth are pnrt_set_frame's; its camera is ignored by this call and
+ * stays current for pnrt_render, pnrt_render_guides and pnrt_reproject.  The
+ * per-pixel camera-ray records pnrt_render keeps are neither used nor invalidated,
+ * and the guide images stay those of the pnrt_set_frame camera (the centre view).
+ * Asynchronous on the stream and ordered like pnrt_render.  `cameras` (n_frames
+ * records, host memory) is copied during the call: the caller may overwrite it as
+ * soon as the call returns, and several calls may be in flight.
+ * Batches follow pnrt_batch_plan's rules with 48 more bytes per path (the camera
+ * ray's record, one per path instead of one per pixel); PNRT_BATCH_BYTES caps that
+ * larger measure, batch b uses cameras[b * frames_per_batch + k], and
+ * pnrt_cameras_batch_plan reports the plan.  Sample moments are updated when
+ * enabled, and for pnrt_render_adaptive's "moments cover the accumulation" rule the
+ * frames count like pnrt_render's.  Profile classes: the camera rays are
+ * PNRT_K_PRIMARY (one launch per batch), the rest as pnrt_render's.
+ *
+ * Errors (nothing queued, accumulation untouched): PNRT_E_STATE before
+ * pnrt_upload_scene or pnrt_set_frame, or under PNRT_KERNEL_V1; PNRT_E_ARG for a bad
+ * selector, first_frame + n_frames > 0xFFFFFFFF, cameras == NULL with n_frames > 0,
+ * or any of the 12 * n_frames floats not finite (the message names the frame);
+ * PNRT_E_TRACE as pnrt_render.  n_frames == 0 or a shard without rows: PNRT_OK,
+ * nothing queued.
+ * Out of scope: an adaptive variant (pnrt_render_adaptive renders the
+ * pnrt_set_frame camera), a device-array form of `cameras`, and per-pixel (rather
+ * than per-frame) lens samples. */
+int pnrt_render_cameras(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames, const pnrt_camera* cameras,
+                        int band_rows, int n_shards, int shard);
+/* pnrt_batch_plan for a pnrt_render_cameras call: the same rules over the larger
+ * per-path measure (batch_bytes includes the 48-byte camera-ray record per path). */
+int pnrt_cameras_batch_plan(pnrt_ctx* ctx, uint32_t n_frames, int band_rows, int n_shards, int shard,
+                            uint32_t* frames_per_batch, uint32_t* n_batches, int64_t* batch_bytes);
+
 /* Redraw semantics (main.cpp:592-596): zero the accumulation image.  Waits
  * for the calls in flight first, and clears a PNRT_E_TRACE fault. */
 int pnrt_reset_accum(pnrt_ctx* ctx);

@@ -121,6 +121,41 @@ int pnrt_camera_update(const float eye[3], const float center[3], const float up
  * pnrt_render traces for that pixel (picking). */
 int pnrt_camera_pixel_ray(const float cam12[12], int px, int py, int width, int height, float ray7_out[7]);
 
+/* The cameras of frames first_frame .. first_frame + n_frames - 1 for libpnrt.so's
+ * pnrt_render_cameras: a box pixel filter and a thin lens around the pinhole camera
+ * cam12 (pnrt_camera_update's out12) of a width x height frame.
+ *   aa_width        the box filter's width in pixels (0 none, 1 one pixel), centred on
+ *                   the reference's own sample point (px / width, py / height), so the
+ *                   image stays registered with the guide images
+ *   lens_radius     in world units (0 pinhole)
+ *   focus_distance  from the eye to the plane in focus; read only when lens_radius > 0
+ * Frame f draws four numbers of a 4-D additive-recurrence sequence, independent of the
+ * path's own Sobol dimensions: with n = (uint32_t)(f + 1) and the multipliers
+ * A = {0xDB4F0B91, 0xBBE05633, 0xA0F2EC77, 0x89E18285} (2^32 * phi^-k, k = 1..4, phi the
+ * real root of x^5 = x + 1; the third made odd),
+ *   u_k = (float)((uint32_t)(n * A_k) >> 8) * 2^-24                        (exact).
+ * The twelve floats of a frame are computed in double from the float inputs, each
+ * rounded to float once; sums run left to right:
+ *   jx = (u1 - 0.5) * aa_width,  jy = (u2 - 0.5) * aa_width
+ *   lens_radius > 0:
+ *     c = ((ll + 0.5 hor) + 0.5 ver) - eye,  |v| = sqrt((vx vx + vy vy) + vz vz),
+ *     s = focus_distance / |c|,  r = lens_radius * sqrt(u3),  phi = (2 pi) * u4
+ *     eye' = (eye + (r cos phi) * (hor / |hor|)) + (r sin phi) * (ver / |ver|)
+ *     ll_f = eye + (ll - eye) * s,  hor' = hor * s,  ver' = ver * s
+ *     (the plane in focus stays fixed while the eye moves over the lens disc, so points
+ *     on it stay sharp: the accumulation-buffer method)
+ *   lens_radius == 0: eye' = eye, hor' = hor, ver' = ver, ll_f = ll, copied
+ *   ll' = (ll_f + (jx / width) * hor') + (jy / height) * ver'   (aa_width == 0: ll_f)
+ * with ll_f, hor', ver' unrounded inside ll'.  aa_width == 0 && lens_radius == 0 returns
+ * cam12 bit for bit in every frame.  cams12_out: 12 * n_frames floats (eye',
+ * ll', hor', ver' per frame).
+ * PNRT_E_ARG (-1): a NULL pointer; width or height < 1; aa_width or lens_radius not
+ * finite or < 0; lens_radius > 0 with a focus_distance that is not finite and > 0;
+ * reserved != 0; a degenerate plane (|c|, |hor| or |ver| zero or not finite). */
+typedef struct { float aa_width, lens_radius, focus_distance; uint32_t reserved; } pnrt_lens_params; /* 16 bytes */
+int pnrt_camera_sequence(const float cam12[12], int width, int height, const pnrt_lens_params* p,
+                         uint32_t first_frame, uint32_t n_frames, float* cams12_out);
+
 /* Camera state (camera.hpp:4-77) and the interactive controls that
  * main.cpp's mouse callbacks call (main.cpp:118-142): left drag ->
  * UpdateRotate(dx, dy), right drag -> UpdateTranslateUV(-dx, dy), scroll ->

@@ -155,6 +155,12 @@ class LumaHistogram(ctypes.Structure):
     _fields_ = [("n_pixels", ctypes.c_int64), ("n_counted", ctypes.c_int64), ("bins", ctypes.c_int64 * LUMA_BINS)]
 
 
+class LensParams(ctypes.Structure):
+    """``pnrt_lens_params`` (16 bytes; include/pnrt_host.h)."""
+    _fields_ = [("aa_width", ctypes.c_float), ("lens_radius", ctypes.c_float), ("focus_distance", ctypes.c_float),
+                ("reserved", ctypes.c_uint32)]
+
+
 QUERY_CLOSEST, QUERY_ANY = 0, 1                # PNRT_QUERY_*
 
 
@@ -193,6 +199,7 @@ def _type_host(lib):
          ctypes.c_uint32, F, F, F, I32, PINT, PINT)
     _sig(lib, "pnrt_mesh_teapot", INT, F, F, F, I32, PINT, PINT)
     _sig(lib, "pnrt_hdr_synthetic", INT, INT, INT, ctypes.c_uint32, F)
+    _sig(lib, "pnrt_camera_sequence", INT, F, INT, INT, ctypes.POINTER(LensParams), ctypes.c_uint32, ctypes.c_uint32, F)
 
 
 def _type_device(lib):
@@ -251,6 +258,9 @@ def _type_device(lib):
          ctypes.POINTER(ctypes.c_float))
     _sig(lib, "pnrt_query_rays", INT, P, F, ctypes.c_int64, INT, ctypes.POINTER(Hit))
     _sig(lib, "pnrt_query_rays_device", INT, P, P, ctypes.c_int64, INT, P)
+    _sig(lib, "pnrt_render_cameras", INT, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(Camera), INT, INT, INT)
+    _sig(lib, "pnrt_cameras_batch_plan", INT, P, ctypes.c_uint32, INT, INT, INT, ctypes.POINTER(ctypes.c_uint32),
+         ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int64))
 
 
 def fptr(a) -> ctypes.POINTER(ctypes.c_float):

@@ -28,7 +28,7 @@ ARCH = os.environ.get("PNRT_OFFLOAD_ARCH", "gfx950")
 DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
                "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pt_adaptive.h", "pt_query.h", "pn_math.h",
-               "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h", "pt_display.h", "pt_refit.h"]
+               "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h", "pt_display.h", "pt_refit.h", "pt_cameras.h"]
 
 
 def _run(cmd, cwd=None):
@@ -188,6 +188,21 @@ def build_refit_abi_caller(force=False):
     return out
 
 
+def build_cameras_abi_caller(force=False):
+    """tests/abi/c_abi_cameras: a camera sequence (pnrt_camera_sequence) rendered with
+    pnrt_render_cameras from a C translation unit (TEST-ONLY; tests/test_gpu_cameras.py)."""
+    src = os.path.join(REPO, "tests", "abi", "c_abi_cameras.c")
+    out = os.path.join(REPO, "tests", "abi", "c_abi_cameras")
+    deps = [src, os.path.join(INC, "pnrt.h"), os.path.join(INC, "pnrt_host.h"), os.path.join(PKG, "libpnrt.so"),
+            os.path.join(PKG, "libpnrt_host.so")]
+    if not all(os.path.exists(d) for d in deps):
+        return None
+    if force or _stale(out, deps):
+        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, src, "-o", out, "-L", PKG, "-lpnrt", "-lpnrt_host", "-lm",
+              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return out
+
+
 def build_oracle(force=False):
     odir = os.path.join(REPO, "oracle")
     _run(["make", "-s", "-C", odir] + (["-B"] if force else []))
@@ -202,6 +217,7 @@ def build_all(force=False):
     build_diag_variants(force)
     build_abi_caller(force)
     build_refit_abi_caller(force)
+    build_cameras_abi_caller(force)
     build_oracle(force)
 
 

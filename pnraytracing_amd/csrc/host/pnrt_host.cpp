@@ -615,6 +615,66 @@ extern "C" int pnrt_camera_pixel_ray(const float cam[12], int px, int py, int wi
     return 0;
 }
 
+// The per-frame cameras of a box pixel filter and a thin lens (pnrt_host.h): double
+// arithmetic on the float inputs in the documented order, one rounding per output.
+extern "C" int pnrt_camera_sequence(const float cam[12], int width, int height, const pnrt_lens_params* p,
+                                    uint32_t first_frame, uint32_t n_frames, float* out) {
+    if (!cam || !p || !out) return fail(-1, "camera_sequence: null");
+    if (width < 1 || height < 1) return fail(-1, "camera_sequence: empty frame");
+    if (!std::isfinite(p->aa_width) || p->aa_width < 0.f) return fail(-1, "camera_sequence: aa_width must be finite and >= 0");
+    if (!std::isfinite(p->lens_radius) || p->lens_radius < 0.f)
+        return fail(-1, "camera_sequence: lens_radius must be finite and >= 0");
+    const bool lens = p->lens_radius > 0.f;
+    if (lens && !(std::isfinite(p->focus_distance) && p->focus_distance > 0.f))
+        return fail(-1, "camera_sequence: focus_distance must be finite and > 0 with a lens");
+    if (p->reserved != 0) return fail(-1, "camera_sequence: reserved must be 0");
+    double eye[3], ll[3], hor[3], ver[3], c[3];
+    for (int i = 0; i < 3; ++i) {
+        eye[i] = cam[i]; ll[i] = cam[3 + i]; hor[i] = cam[6 + i]; ver[i] = cam[9 + i];
+        c[i] = ((ll[i] + 0.5 * hor[i]) + 0.5 * ver[i]) - eye[i];
+    }
+    auto len = [](const double* v) { return std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); };
+    const double lc = len(c), lh = len(hor), lv = len(ver);
+    if (!(std::isfinite(lc) && lc > 0.0 && std::isfinite(lh) && lh > 0.0 && std::isfinite(lv) && lv > 0.0))
+        return fail(-1, "camera_sequence: degenerate image plane");
+    static const uint32_t A[4] = {0xDB4F0B91u, 0xBBE05633u, 0xA0F2EC77u, 0x89E18285u};
+    const double aa = p->aa_width;
+    for (uint32_t k = 0; k < n_frames; ++k) {
+        const uint32_t n = first_frame + k + 1u;
+        double u[4];
+        for (int d = 0; d < 4; ++d) u[d] = (double)((float)((uint32_t)(n * A[d]) >> 8) * 0x1p-24f);
+        float* o = out + 12 * (size_t)k;
+        double llf[3], h2[3], v2[3];
+        if (lens) {
+            const double s = (double)p->focus_distance / lc;
+            const double r = (double)p->lens_radius * std::sqrt(u[2]), phi = (2.0 * 3.14159265358979323846) * u[3];
+            const double a = r * std::cos(phi), b = r * std::sin(phi);
+            for (int i = 0; i < 3; ++i) {
+                o[i] = (float)((eye[i] + a * (hor[i] / lh)) + b * (ver[i] / lv));
+                llf[i] = eye[i] + (ll[i] - eye[i]) * s;
+                h2[i] = hor[i] * s;
+                v2[i] = ver[i] * s;
+                o[6 + i] = (float)h2[i];
+                o[9 + i] = (float)v2[i];
+            }
+        } else {
+            for (int i = 0; i < 3; ++i) {
+                o[i] = cam[i]; o[6 + i] = cam[6 + i]; o[9 + i] = cam[9 + i];
+                llf[i] = ll[i]; h2[i] = hor[i]; v2[i] = ver[i];
+            }
+        }
+        if (p->aa_width > 0.f) {
+            const double jx = (u[0] - 0.5) * aa, jy = (u[1] - 0.5) * aa;
+            for (int i = 0; i < 3; ++i) o[3 + i] = (float)((llf[i] + (jx / width) * h2[i]) + (jy / height) * v2[i]);
+        } else if (lens) {
+            for (int i = 0; i < 3; ++i) o[3 + i] = (float)llf[i];
+        } else {
+            for (int i = 0; i < 3; ++i) o[3 + i] = cam[3 + i];
+        }
+    }
+    return 0;
+}
+
 // ---- Camera (camera.hpp:4-77): state + the interactive controls main.cpp's
 // mouse callbacks drive (main.cpp:118-142): left drag UpdateRotate, right drag
 // UpdateTranslateUV, scroll UpdateFov.  glm-exact float arithmetic.

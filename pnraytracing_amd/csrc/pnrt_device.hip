@@ -29,6 +29,7 @@
 #include "pt_reproject.h"
 #include "pt_display.h"
 #include "pt_refit.h"
+#include "pt_cameras.h"
 
 __global__ void pt_pack_rows_kernel(const float4* accum, float4* dst, int width, int rows, int band,
                                     int n_shards, int shard) {
@@ -148,6 +149,9 @@ struct pnrt_ctx {
         void* wf = nullptr;         size_t wf_cap = 0;
         uint2* ovf = nullptr;       size_t ovf_cap = 0;
         bool blend_pending = false;  // ev_blend guards the colour buffer's last reader
+        // pnrt_render_cameras: the batch's camera-ray record per path slot and its camera table
+        float4* camrec = nullptr;   size_t camrec_cap = 0;
+        float* camtab = nullptr;    size_t camtab_cap = 0;
     };
     Pipe pipe[WF_PIPES];
     unsigned n_pipes_small = WF_PIPES;     // pipes small calls rotate over (pipes_init)
@@ -220,6 +224,15 @@ struct pnrt_ctx {
     // in-place geometry edits (pnrt_update_vertices; pt_refit.h): none until the first call
     float* rf_stage = nullptr;             size_t rf_stage_cap = 0;    // the host form's staging buffer: vertex records in
     RefitResult* rf_res = nullptr;         // the root box and the non-finite flag the host reads back
+    // per-frame cameras (pnrt_render_cameras; pt_cameras.h): none until the first call.  A call's array is
+    // copied into a pinned staging block, from which each batch's table is copied to its pipe in stream
+    // order; a block is reused once the event behind its call's last copy has completed
+    struct CamStage {
+        float* host = nullptr;  size_t cap = 0;
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+    };
+    std::vector<CamStage> cam_stage;
 };
 
 static int set_err(pnrt_ctx* c, int code, const std::string& m) {
@@ -515,7 +528,8 @@ static int report_trace_diag(pnrt_ctx* c, const WfBufs& b, hipStream_t st, int b
 // its colours land in frame slots [0, cf) of `colors`.
 static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const WfLayout& L, hipStream_t st,
                         const float4* primary, float4* colors, bool alone, bool one, hipEvent_t stage = nullptr,
-                        const WfAdapt* ad = nullptr) {     // ad: an adaptive batch's slots (pt_adaptive.h)
+                        const WfAdapt* ad = nullptr,       // ad: an adaptive batch's slots (pt_adaptive.h)
+                        const WfCams* cm = nullptr) {      // cm: a camera batch's table (pt_cameras.h; primary = its records)
     WfBufs b = L.b;
     if (b.n > WF_META_SLOT) return set_err(c, PNRT_E_ARG, "render: too many paths per batch");
     // the cooperative finish of closest-hit rays pays where the drain leaves the chip
@@ -531,6 +545,7 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
     {   // path state + bounce-0 sampling
         ProfScope ps(c, PNRT_K_GEN, st);
         if (ad) hipLaunchKernelGGL(pt_wf_gen_setup<WfAdapt>, g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
+        else if (cm) hipLaunchKernelGGL(pt_wf_gen_setup<WfCams>, g, dim3(256), 0, st, s, fp, b, primary, colors, *cm);
         else hipLaunchKernelGGL(pt_wf_gen_setup<>, g, dim3(256), 0, st, s, fp, b, primary, colors);
     }
     HIPCHK(c, hipGetLastError());
@@ -565,6 +580,10 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
                 hipLaunchKernelGGL((pt_wf_shade_setup<true, WfAdapt>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
             else if (ad)
                 hipLaunchKernelGGL((pt_wf_shade_setup<false, WfAdapt>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
+            else if (cm && fin)
+                hipLaunchKernelGGL((pt_wf_shade_setup<true, WfCams>), g, dim3(256), 0, st, s, fp, b, primary, colors, *cm);
+            else if (cm)
+                hipLaunchKernelGGL((pt_wf_shade_setup<false, WfCams>), g, dim3(256), 0, st, s, fp, b, primary, colors, *cm);
             else if (fin)
                 hipLaunchKernelGGL(pt_wf_shade_setup<true>, g, dim3(256), 0, st, s, fp, b, primary, colors);
             else
@@ -596,20 +615,22 @@ static bool parse_batch_bytes(const char* s, uint64_t* out) {
 static size_t frame_paths(int width, int rows) {
     return (size_t)((width + 7) / 8) * (size_t)((rows + 7) / 8) * 64;
 }
-static size_t batch_bytes(size_t per_frame, size_t pix, uint32_t k) {
-    return wf_bytes(per_frame * k) + pix * 16 * k;
+// (per_path: further bytes per path slot -- pnrt_render_cameras' camera-ray records)
+#define CAM_REC_BYTES 48       // pt_primary_wf's record (q0, q1, q2), one per path slot of a camera batch
+static size_t batch_bytes(size_t per_frame, size_t pix, uint32_t k, size_t per_path = 0) {
+    return wf_bytes(per_frame * k) + pix * 16 * k + per_frame * k * per_path;
 }
 // Frames per batch of a call of nf frames (the one plan: render_wavefront and
 // pnrt_batch_plan): at most WF_MAX_CHUNK_FRAMES, few enough that every path slot
 // fits the path state's slot field (large frames take fewer per batch), and under
 // PNRT_BATCH_BYTES the largest count whose batch_bytes fit the cap -- one frame when
 // not even one does.  0: a frame too large for one batch.
-static uint32_t plan_chunk(const pnrt_ctx* c, size_t per_frame, size_t pix, uint32_t nf) {
+static uint32_t plan_chunk(const pnrt_ctx* c, size_t per_frame, size_t pix, uint32_t nf, size_t per_path = 0) {
     if (per_frame == 0 || per_frame > (size_t)WF_META_SLOT) return 0;
     const uint32_t fit = (uint32_t)std::min<size_t>(WF_MAX_CHUNK_FRAMES, (size_t)WF_META_SLOT / per_frame);
     uint32_t chunk = nf < fit ? nf : fit;
     // (batch_bytes grows with the frame count, so the first count that fits is the largest)
-    while (c->batch_bytes_cap && chunk > 1 && batch_bytes(per_frame, pix, chunk) > c->batch_bytes_cap) --chunk;
+    while (c->batch_bytes_cap && chunk > 1 && batch_bytes(per_frame, pix, chunk, per_path) > c->batch_bytes_cap) --chunk;
     return chunk;
 }
 
@@ -707,6 +728,7 @@ struct BatchRoute {
     bool alone, one, stagger;
     int ovf_stride, tiles_x;
     const WfAdapt* ad;       // an adaptive call's active-tile list, or null
+    const float* cams;       // pnrt_render_cameras: the call's cameras (pinned host memory, 12 floats per frame), or null
 };
 // The batches of one call on pipe P: per group of `chunk` frames one batch (gen ->
 // {trace -> shade} x depth) of per_frame path slots per frame on R.w, then the
@@ -727,8 +749,24 @@ static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pn
         a.b.first_frame = first + f0;
         if (f0 && w != c->stream) HIPCHK(c, hipStreamWaitEvent(w, P.ev_blend, 0));   // the previous group's blend has read the colours
         const bool last = f0 + cf >= nf;
-        if ((rc = render_batch(c, s, fp, a, w, P.primary, P.colors, R.alone, R.one, R.stagger && last ? P.ev_stage : nullptr,
-                               R.ad)))
+        const float4* primary = P.primary;
+        WfCams cm{nullptr};
+        if (R.cams) {
+            // the batch's cameras, then its camera rays: one per path slot (pt_cameras.h).  Both follow
+            // the previous batch's kernels on w, the last readers of the table and the records
+            cm.table = P.camtab;
+            primary = P.camrec;
+            HIPCHK(c, hipMemcpyAsync(P.camtab, R.cams + 12 * (size_t)f0, (size_t)cf * 48, hipMemcpyHostToDevice, w));
+            ProfScope ps(c, PNRT_K_PRIMARY, w);
+            const unsigned gp = (unsigned)std::min<size_t>(((size_t)a.b.n + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
+            if (s.has_leaf_table)
+                hipLaunchKernelGGL((pt_camera_rays_wf<WF_STACK, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, cm, P.camrec);
+            else
+                hipLaunchKernelGGL((pt_camera_rays_wf<WF_STACK, false>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, cm, P.camrec);
+            HIPCHK(c, hipGetLastError());
+        }
+        if ((rc = render_batch(c, s, fp, a, w, primary, P.colors, R.alone, R.one, R.stagger && last ? P.ev_stage : nullptr,
+                               R.ad, R.cams ? &cm : nullptr)))
             return rc;
         if (R.stagger && last) P.stage_set = true;
         if (w != c->stream) {
@@ -762,13 +800,17 @@ static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pn
 // frame-ordered blend on the context stream.  Consecutive calls are independent
 // path sets, so running them concurrently changes nothing in the result; the
 // blends keep frame order.
-static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, uint32_t first, uint32_t nf) {
+// cams: pnrt_render_cameras' call -- the cameras of its nf frames in pinned host memory; the batches
+// are planned with the camera-ray records' bytes, trace their own camera rays (run_batches) and
+// leave the pipe's per-pixel records and their key alone.
+static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, uint32_t first, uint32_t nf,
+                            const float* cams = nullptr) {
     int rc;
     if ((rc = pipes_init(c))) return rc;
     const size_t pix = (size_t)fp.rows * c->width;
     const int tiles_x = (c->width + 7) / 8;
     const size_t per_frame = frame_paths(c->width, fp.rows);
-    const uint32_t chunk = plan_chunk(c, per_frame, pix, nf);   // frames per batch
+    const uint32_t chunk = plan_chunk(c, per_frame, pix, nf, cams ? CAM_REC_BYTES : 0);   // frames per batch
     if (chunk == 0) return set_err(c, PNRT_E_ARG, "render: frame too large for one batch");
     // calls in flight by call size (paths per batch): small (< 5M: multi-GPU shares)
     // 4 with > 4 hardware queues; 5M-12M 2 -- their launches are long enough to fill
@@ -808,6 +850,13 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
     // the same size reallocates (a reallocation waits for all calls in flight)
     for (unsigned q = 0; q < npipes; ++q)
         if ((rc = pipe_size(c, c->pipe[(pi + q) % npipes], pix, pix * 16 * chunk, per_frame * chunk, ovf_bytes))) return rc;
+    if (cams)
+        for (unsigned q = 0; q < npipes; ++q) {
+            pnrt_ctx::Pipe& Q = c->pipe[(pi + q) % npipes];
+            if ((rc = grow(c, (void**)&Q.camrec, &Q.camrec_cap, per_frame * chunk * CAM_REC_BYTES)) ||
+                (rc = grow(c, (void**)&Q.camtab, &Q.camtab_cap, (size_t)WF_MAX_CHUNK_FRAMES * 48)))
+                return rc;
+        }
     ++c->ncall;
     // A call with nothing in flight runs on the caller's stream itself: no worker
     // stream to order against it, so no event wait before its first kernel and no
@@ -822,9 +871,15 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
         HIPCHK(c, hipStreamWaitEvent(w, c->pipe[prev_pipe].ev_stage, 0));
     P.stage_set = false;
     // the pipe's primary records: traced now, or still valid from an earlier call (PrimKey)
-    if ((rc = ensure_primary(c, s, fp, w, P.ovf, ovf_stride, P.primary, P.prim))) return rc;
-    const BatchRoute R = {w, alone, one, stagger, ovf_stride, tiles_x, nullptr};
-    return run_batches(c, s, fp, P, R, per_frame, chunk, first, nf);
+    if (!cams && (rc = ensure_primary(c, s, fp, w, P.ovf, ovf_stride, P.primary, P.prim))) return rc;
+    const BatchRoute R = {w, alone, one, stagger, ovf_stride, tiles_x, nullptr, cams};
+    if ((rc = run_batches(c, s, fp, P, R, per_frame, chunk, first, nf))) return rc;
+    if (cams) {                 // behind the call's last table copy: the staging block is free once it completes
+        pnrt_ctx::CamStage& S = c->cam_stage.back();
+        HIPCHK(c, hipEventRecord(S.ev, w));
+        S.pending = true;
+    }
+    return PNRT_OK;
 }
 
 // pnrt_render_adaptive's frames: the batches over the active tiles' path slots.  The
@@ -846,7 +901,7 @@ static int render_adaptive(pnrt_ctx* c, const DevScene& s, const FrameParams& fp
     hipStream_t w = (alone && WF_ALONE_ON_CALLER) ? c->stream : P.w;
     P.stage_set = false;
     if ((rc = ensure_primary(c, s, fp, w, P.ovf, ovf_stride, P.primary, P.prim))) return rc;
-    const BatchRoute R = {w, alone, c->serial, false, ovf_stride, (c->width + 7) / 8, &ad};
+    const BatchRoute R = {w, alone, c->serial, false, ovf_stride, (c->width + 7) / 8, &ad, nullptr};
     return run_batches(c, s, fp, P, R, per_frame, chunk, first, nf);
 }
 
@@ -1173,6 +1228,7 @@ void pnrt_destroy(pnrt_ctx* c) {
     (void)sync_all(c);
     for (auto& P : c->pipe) {
         (void)hipFree(P.primary); (void)hipFree(P.colors); (void)hipFree(P.wf); (void)hipFree(P.ovf);
+        (void)hipFree(P.camrec); (void)hipFree(P.camtab);
         if (P.w) (void)hipStreamDestroy(P.w);
         if (P.ev_join) (void)hipEventDestroy(P.ev_join);
         if (P.ev_blend) (void)hipEventDestroy(P.ev_blend);
@@ -1189,6 +1245,10 @@ void pnrt_destroy(pnrt_ctx* c) {
     (void)hipFree(c->rp_counts);
     (void)hipFree(c->disp); (void)hipFree(c->luma_hist);
     (void)hipFree(c->rf_stage); (void)hipFree(c->rf_res);
+    for (auto& S : c->cam_stage) {
+        if (S.host) (void)hipHostFree(S.host);
+        if (S.ev) (void)hipEventDestroy(S.ev);
+    }
 
     for (auto& p : c->ev_pending) { c->ev_pool.push_back(p.second.first); c->ev_pool.push_back(p.second.second); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1868,25 +1928,92 @@ int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int
     return render_wavefront(c, s, fp, first, nf);
 }
 
-int pnrt_batch_plan(pnrt_ctx* c, uint32_t nf, int band, int nsh, int shard, uint32_t* frames_per_batch,
-                    uint32_t* n_batches, int64_t* bytes) {
+// A staging block for a call's cameras, moved to the back of the list: one whose last copy has
+// completed (grown if too small), or a new one.
+static int cam_stage_get(pnrt_ctx* c, size_t bytes) {
+    size_t at = c->cam_stage.size();
+    for (size_t i = 0; i < c->cam_stage.size() && at == c->cam_stage.size(); ++i) {
+        pnrt_ctx::CamStage& S = c->cam_stage[i];
+        if (!S.pending || hipEventQuery(S.ev) == hipSuccess) at = i;
+    }
+    if (at == c->cam_stage.size()) {
+        pnrt_ctx::CamStage S;
+        HIPCHK(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
+        c->cam_stage.push_back(S);
+    }
+    std::swap(c->cam_stage[at], c->cam_stage.back());
+    pnrt_ctx::CamStage& S = c->cam_stage.back();
+    S.pending = false;
+    if (S.cap < bytes) {
+        if (S.host) (void)hipHostFree(S.host);
+        S.host = nullptr; S.cap = 0;
+        const size_t cap = std::max<size_t>(bytes, 4096);
+        HIPCHK(c, hipHostMalloc((void**)&S.host, cap, hipHostMallocDefault));
+        S.cap = cap;
+    }
+    return PNRT_OK;
+}
+
+int pnrt_render_cameras(pnrt_ctx* c, uint32_t first, uint32_t nf, const pnrt_camera* cameras, int band, int nsh, int shard) {
     if (!c) return PNRT_E_ARG;
-    if (!c->has_frame) return set_err(c, PNRT_E_STATE, "batch_plan: set_frame first");
-    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "batch_plan: bad shard selector");
+    if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, "render_cameras: upload_scene and set_frame first");
+    if (c->kernel == 1)
+        return set_err(c, PNRT_E_STATE, "render_cameras: PNRT_KERNEL_V1 renders the pnrt_set_frame camera only");
+    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "render_cameras: bad shard selector");
+    if ((uint64_t)first + nf > 0xFFFFFFFFull)
+        return set_err(c, PNRT_E_ARG,
+                       "render_cameras: first_frame + n_frames exceeds 0xFFFFFFFF (the last frame number is 0xFFFFFFFE)");
+    if (nf > 0 && !cameras) return set_err(c, PNRT_E_ARG, "render_cameras: cameras is NULL");
+    static_assert(sizeof(pnrt_camera) == 48, "twelve floats per camera");
+    const float* cf = reinterpret_cast<const float*>(cameras);
+    for (uint64_t i = 0; i < 12ull * nf; ++i)
+        if (!std::isfinite(cf[i]))
+            return set_err(c, PNRT_E_ARG, "render_cameras: a camera component is not finite: frame " +
+                                              std::to_string((uint64_t)first + i / 12) + " (cameras[" + std::to_string(i / 12) +
+                                              "], float " + std::to_string(i % 12) + ")");
+    if (int rc = check_fault(c)) return rc;      // an earlier call's trace fault (completed work)
+    if (nf == 0) return PNRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const FrameParams fp = call_frame_params(c, first, nf, band, nsh, shard);
+    if (fp.rows == 0) return PNRT_OK;
+    if (!c->moments_on) c->mom_cover = false;    // frames the moments do not count, as pnrt_render's
+    const DevScene s = launch_scene(c);
+    // the array is the caller's again when this returns: the batches read the copy
+    if (int rc = cam_stage_get(c, (size_t)nf * 48)) return rc;
+    std::memcpy(c->cam_stage.back().host, cf, (size_t)nf * 48);
+    return render_wavefront(c, s, fp, first, nf, c->cam_stage.back().host);
+}
+
+// pnrt_batch_plan / pnrt_cameras_batch_plan: the plan of a call whose paths hold per_path further bytes.
+static int batch_plan(pnrt_ctx* c, const std::string& who, size_t per_path, uint32_t nf, int band, int nsh, int shard,
+                      uint32_t* frames_per_batch, uint32_t* n_batches, int64_t* bytes) {
+    if (!c) return PNRT_E_ARG;
+    if (!c->has_frame) return set_err(c, PNRT_E_STATE, who + ": set_frame first");
+    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, who + ": bad shard selector");
     uint32_t chunk = 0, nb = 0;
     int64_t by = 0;
     const int rows = shard_rows(c->height, band, nsh, shard);
-    if (nf > 0 && rows > 0) {                    // (pnrt_render queues nothing otherwise)
+    if (nf > 0 && rows > 0) {                    // (the render call queues nothing otherwise)
         const size_t per_frame = frame_paths(c->width, rows), pix = (size_t)rows * c->width;
-        chunk = plan_chunk(c, per_frame, pix, nf);
-        if (chunk == 0) return set_err(c, PNRT_E_ARG, "batch_plan: frame too large for one batch");
+        chunk = plan_chunk(c, per_frame, pix, nf, per_path);
+        if (chunk == 0) return set_err(c, PNRT_E_ARG, who + ": frame too large for one batch");
         nb = nf / chunk + (nf % chunk ? 1u : 0u);
-        by = (int64_t)batch_bytes(per_frame, pix, chunk);
+        by = (int64_t)batch_bytes(per_frame, pix, chunk, per_path);
     }
     if (frames_per_batch) *frames_per_batch = chunk;
     if (n_batches) *n_batches = nb;
     if (bytes) *bytes = by;
     return PNRT_OK;
+}
+
+int pnrt_cameras_batch_plan(pnrt_ctx* c, uint32_t nf, int band, int nsh, int shard, uint32_t* frames_per_batch,
+                            uint32_t* n_batches, int64_t* bytes) {
+    return batch_plan(c, "cameras_batch_plan", CAM_REC_BYTES, nf, band, nsh, shard, frames_per_batch, n_batches, bytes);
+}
+
+int pnrt_batch_plan(pnrt_ctx* c, uint32_t nf, int band, int nsh, int shard, uint32_t* frames_per_batch,
+                    uint32_t* n_batches, int64_t* bytes) {
+    return batch_plan(c, "batch_plan", 0, nf, band, nsh, shard, frames_per_batch, n_batches, bytes);
 }
 
 int pnrt_reset_accum(pnrt_ctx* c) {

@@ -187,9 +187,22 @@ struct WfAdapt {
     const WfTile* tiles;
     uint32_t n_tiles;            // entries of the list
 };
-// the kernels' trailing argument pack: nothing (no list), or the list
+// A camera batch (pnrt_render_cameras, pt_cameras.h) renders frame
+// slot k with its own pinhole camera: twelve floats (eye, lower_left, horizontal,
+// vertical) at table[12 * k], and the camera ray's record of every path slot at
+// primary[3 * slot] instead of one per pixel.  The slots are wf_coords' own.
+struct WfCams {
+    const float* table;          // [12 * chunk_frames]
+};
+// the kernels' trailing argument pack: nothing (no list), the list, or the camera table
 PN_DEV WfAdapt wf_adapt() { return WfAdapt{nullptr, 0u}; }
 PN_DEV WfAdapt wf_adapt(const WfAdapt& ad) { return ad; }
+PN_DEV WfAdapt wf_adapt(const WfCams&) { return WfAdapt{nullptr, 0u}; }
+PN_DEV WfCams wf_cams() { return WfCams{nullptr}; }
+PN_DEV WfCams wf_cams(const WfAdapt&) { return WfCams{nullptr}; }
+PN_DEV WfCams wf_cams(const WfCams& cm) { return cm; }
+template <class T, class... AD>
+inline constexpr bool wf_pack_is = (std::is_same_v<T, AD> || ...);
 // -> whether the slot's pixel is active (a lane of an inactive pixel starts no path)
 PN_DEV bool wf_coords_adaptive(const WfBufs& b, const WfAdapt& ad, uint32_t s, int& x, int& lr, int& k) {
     uint32_t per_tile = 64u * (uint32_t)b.chunk_frames;
@@ -257,6 +270,25 @@ PN_DEV void wf_put_color(const WfBufs& b, const FrameParams& fp, float4* colors,
 // the primary record of local row lr, column x
 PN_DEV const float4* wf_primary(const WfBufs& b, const FrameParams& fp, const float4* primary, int lr, int x) {
     return primary + 3 * PT_CHECK(b.fault, (size_t)lr * fp.width + x, (size_t)fp.rows * fp.width, PT_SITE_PRIMARY);
+}
+// ... of a camera batch: the record of the path's own camera ray, at its slot
+template <bool CAMS>
+PN_DEV const float4* wf_primary_of(const WfBufs& b, const FrameParams& fp, const float4* primary, uint32_t slot, int lr, int x) {
+    if constexpr (CAMS) return primary + 3 * PT_CHECK(b.fault, (size_t)slot, (size_t)b.n, PT_SITE_PRIMARY);
+    else return wf_primary(b, fp, primary, lr, x);
+}
+// CameraGetRay (camera_dir, pt_passes.h: the same operations in the same order) for
+// frame slot k's camera of a camera batch.  k is uniform over the wave (a wave's 64
+// slots are one tile of one frame), so the twelve floats are scalar loads.
+PN_DEV f3 wf_camera_dir(const FrameParams& fp, const WfCams& cm, int k, int px, int py, f3& eye) {
+    // (read through the constant address space: no kernel writes the table, and a uniform
+    // address there selects s_load -- a plain global load stays a vector load in a kernel
+    // that also stores)
+    typedef const float __attribute__((address_space(4))) cfloat;
+    cfloat* t = (cfloat*)(cm.table + 12 * (size_t)__builtin_amdgcn_readfirstlane(k));
+    eye = mk3(t[0], t[1], t[2]);
+    float sx = (float)px / (float)fp.width, sy = (float)py / (float)fp.height;
+    return normalize(sub(add(add(mk3(t[3], t[4], t[5]), smul(sx, mk3(t[6], t[7], t[8]))), smul(sy, mk3(t[9], t[10], t[11]))), eye));
 }
 
 // Path state a bounce's setup starts from (in registers: the fused kernels
@@ -630,12 +662,14 @@ PN_DEV void wf_enqueue(const WfBufs& b, uint32_t i, uint32_t nfl, const BounceRa
 
 // ---- gen + bounce-0 setup: start every path from its pixel's primary hit -------------------
 // AD: empty (pt_wf_gen_setup<>, the slots of a pnrt_render batch: the kernel's five
-// arguments) or WfAdapt (the slots of an adaptive batch, through its list).
+// arguments), WfAdapt (the slots of an adaptive batch, through its list) or WfCams (a
+// camera batch: `primary` holds a record per slot, V comes from the frame's camera).
 template <class... AD>
 __global__ void __launch_bounds__(256, WF_GEN_WAVES) pt_wf_gen_setup(DevScene s, FrameParams fp, WfBufs b, const float4* primary,
                                                        float4* colors, AD... adv) {
-    constexpr bool ADAPT = sizeof...(AD) != 0;
+    constexpr bool ADAPT = wf_pack_is<WfAdapt, AD...>, CAMS = wf_pack_is<WfCams, AD...>;
     const WfAdapt ad = wf_adapt(adv...);
+    [[maybe_unused]] const WfCams cm = wf_cams(adv...);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;     // path slot
     wf_reset_counters(b);
     wf_live_init();
@@ -659,7 +693,7 @@ __global__ void __launch_bounds__(256, WF_GEN_WAVES) pt_wf_gen_setup(DevScene s,
         if constexpr (ADAPT) active = wf_coords_adaptive(b, ad, i, x, lr, k);    // (a clear mask bit: no path, no colour)
         else wf_coords(b, i, x, lr, k);
         if (active && x < fp.width && lr < fp.rows) {
-            const float4* rec = wf_primary(b, fp, primary, lr, x);
+            const float4* rec = wf_primary_of<CAMS>(b, fp, primary, i, lr, x);
             const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
             const int mt = __float_as_int(q0.w);
             const f3 base = mk3(q2.y, q2.z, q2.w);
@@ -672,7 +706,8 @@ __global__ void __launch_bounds__(256, WF_GEN_WAVES) pt_wf_gen_setup(DevScene s,
                 frame = b.first_frame + (uint32_t)k;
                 q.P = mk3(q0.x, q0.y, q0.z); q.N = mk3(q1.x, q1.y, q1.z);
                 q.u = q1.w; q.v = q2.x; q.mt = mt;
-                q.V = neg(camera_dir(fp, x, py));
+                if constexpr (CAMS) { f3 eye; q.V = neg(wf_camera_dir(fp, cm, k, x, py, eye)); }
+                else q.V = neg(camera_dir(fp, x, py));
                 q.cw = mk3(1.f, 1.f, 1.f);
                 q.Lo = mk3(0.f, 0.f, 0.f);
                 q.seed = ((uint32_t)x * 1973u + (uint32_t)py * 9277u + frame * 26699u) | 1u;
@@ -1857,7 +1892,7 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, PT_PRIM_WF_WAVES) pt_primary_w
 // ---- shade: MIS, continuation hit, next bounce or final colour (:936-972) --------------------
 // Path entry i of the read set.  Returns whether the path continues; then q,
 // bounce, slot and the pixel / frame carry its next bounce to the setup.
-template <bool ADAPT>
+template <bool ADAPT, bool CAMS = false>
 PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs& b, const WfAdapt& ad, const float4* primary,
                           float4* colors, uint32_t i, PathIn& q, int& bounce, uint32_t& slot, int& x, int& py,
                           uint32_t& frame) {
@@ -1900,7 +1935,7 @@ PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs
             f3 enLi = env_color(s, normalize(L));
             Lo = add(Lo, divs(muls(mul(mul(cw, enLi), dBRDF), NdotL), dPDF));
         }
-        const float4 q2 = wf_primary(b, fp, primary, lr, x)[2];     // the primary hit's base colour
+        const float4 q2 = wf_primary_of<CAMS>(b, fp, primary, slot, lr, x)[2];     // the primary hit's base colour
         wf_put_color<ADAPT>(b, fp, colors, slot, k, lr, x, add(mk3(q2.y, q2.z, q2.w), Lo));
         return false;
     }
@@ -1911,7 +1946,7 @@ PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs
     cw = mul(cw, divs(muls(dBRDF, NdotL), dPDF));
     ++bounce;
     if (bounce >= fp.max_depth) {
-        const float4 q2 = wf_primary(b, fp, primary, lr, x)[2];
+        const float4 q2 = wf_primary_of<CAMS>(b, fp, primary, slot, lr, x)[2];
         wf_put_color<ADAPT>(b, fp, colors, slot, k, lr, x, add(mk3(q2.y, q2.z, q2.w), Lo));
         return false;
     }
@@ -1931,8 +1966,9 @@ PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs
 template <bool FINAL, class... AD>
 __global__ void __launch_bounds__(256, FINAL ? 8 : WF_SHADE_WAVES) pt_wf_shade_setup(DevScene s, FrameParams fp, WfBufs b,
                                                                      const float4* primary, float4* colors, AD... adv) {
-    constexpr bool ADAPT = sizeof...(AD) != 0;
+    constexpr bool ADAPT = wf_pack_is<WfAdapt, AD...>, CAMS = wf_pack_is<WfCams, AD...>;
     const WfAdapt ad = wf_adapt(adv...);
+    [[maybe_unused]] const WfCams cm = wf_cams(adv...);
     // the block's live paths are its first b.rd.bcount[block] entries
     wf_check_drained(b);                      // (the previous trace's counters, then reset)
     if (!FINAL) wf_reset_counters(b);
@@ -1948,7 +1984,7 @@ __global__ void __launch_bounds__(256, FINAL ? 8 : WF_SHADE_WAVES) pt_wf_shade_s
     PathIn q;
     int bounce = 0, x = 0, py = 0;
     uint32_t slot = 0, frame = 0;
-    if (threadIdx.x < live) cont = wf_shade_path<ADAPT>(s, fp, b, ad, primary, colors, i, q, bounce, slot, x, py, frame);
+    if (threadIdx.x < live) cont = wf_shade_path<ADAPT, CAMS>(s, fp, b, ad, primary, colors, i, q, bounce, slot, x, py, frame);
     if (FINAL) return;                        // bounce + 1 == max_depth: cont is false for every path
     const uint32_t j = blockIdx.x * 256u + wf_entry_rank(cont);
     uint32_t nfl = 0;

@@ -98,6 +98,10 @@ class ShardedFrame:
         """Asynchronously render frames first..first+n-1 of this rank's rows."""
         self.tracer.render(first_frame, n_frames, self.band, self.world, self.rank)
 
+    def render_cameras(self, first_frame: int, cameras):
+        """``render`` with a camera per frame (``PathTracer.render_cameras``) over this rank's rows."""
+        self.tracer.render_cameras(first_frame, cameras, self.band, self.world, self.rank)
+
     def _gather(self) -> torch.Tensor | None:
         """Pack this rank's rows, gather on rank 0; returns the H x W x 4 image
         (row 0 = bottom) on rank 0 and None elsewhere."""

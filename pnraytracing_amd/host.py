@@ -128,6 +128,23 @@ def camera_pixel_ray(camera, px: int, py: int, width: int, height: int) -> np.nd
     return out
 
 
+def camera_sequence(camera, width: int, height: int, first_frame: int, n_frames: int, aa_width: float = 1.0,
+                    lens_radius: float = 0.0, focus_distance: float = 0.0) -> np.ndarray:
+    """The cameras of frames ``first_frame .. first_frame + n_frames - 1`` for
+    ``PathTracer.render_cameras`` (pnrt_camera_sequence): a box pixel filter ``aa_width``
+    pixels wide and a thin lens of ``lens_radius`` world units focused ``focus_distance``
+    from the eye, around the pinhole ``camera``.  (n_frames, 12) float32."""
+    for name, v in (("first_frame", first_frame), ("n_frames", n_frames)):
+        if not 0 <= v <= 0xFFFFFFFF:
+            raise ValueError(f"camera_sequence: {name} = {v} is outside 0 .. 2**32 - 1")
+    cam = np.ascontiguousarray(camera, np.float32).reshape(12)
+    out = np.zeros((int(n_frames), 12), np.float32)
+    p = N.LensParams(float(aa_width), float(lens_radius), float(focus_distance), 0)
+    _check(N.host_lib().pnrt_camera_sequence(N.fptr(cam), int(width), int(height), ctypes.byref(p), int(first_frame),
+                                             int(n_frames), N.fptr(out)), "camera_sequence")
+    return out
+
+
 def decode_rgbe(data: bytes) -> np.ndarray:
     """stbi_loadf on a Radiance .hdr (3 channels, row 0 = first scanline)."""
     buf = np.frombuffer(data, np.uint8).copy()

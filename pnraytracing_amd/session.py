@@ -84,6 +84,43 @@ class InteractiveSession:
         self.max_bounce_depth = max_bounce_depth
         self.frame_count = 0
         self._rendered_camera = None                 # uniforms of the last call that rendered (reproject's `from`)
+        self._lens = None                            # set_lens: (aa_width, lens_radius, focus_distance)
+
+    def set_lens(self, aa_width: float = 1.0, lens_radius: float = 0.0, focus_distance: float | None = None):
+        """Anti-aliasing and depth of field for the still frames: from now on ``frame()``
+        and ``frame_counted()`` render frame ``frame_count`` with that frame's camera of
+        ``host.camera_sequence`` (a box pixel filter ``aa_width`` pixels wide, a thin lens of
+        ``lens_radius`` world units focused ``focus_distance`` from the eye -- ``focus_on``
+        sets it from a pixel) through ``PathTracer.render_cameras``.  A redraw stays the
+        reference's un-jittered depth-1 frame 0.  Never called, nothing changes."""
+        if lens_radius > 0 and focus_distance is None:
+            focus_distance = self._lens[2] if self._lens else None
+            if focus_distance is None:
+                raise ValueError("set_lens: a lens needs a focus_distance (or focus_on(px, py) first)")
+        self._lens = (float(aa_width), float(lens_radius), None if focus_distance is None else float(focus_distance))
+
+    def focus_on(self, px: int, py: int) -> bool:
+        """Focus on what is under pixel (px, py): ``focus_distance`` becomes the distance of
+        ``pick(px, py)``'s hit along the view axis (the plane in focus is parallel to the
+        image plane).  Nothing changes on a miss.  Returns whether the pixel hit."""
+        rec = self.pick(px, py)
+        if not rec["hit"]:
+            return False
+        s = self.camera.state
+        eye = np.array(list(s.eye), np.float64)
+        axis = -np.array(list(s.w), np.float64)      # the view direction (camera.hpp: w = normalize(eye - center))
+        d = float(np.dot(np.asarray(rec["position"], np.float64) - eye, axis))
+        if not d > 0:
+            return False
+        aa, radius = (self._lens[0], self._lens[1]) if self._lens else (1.0, 0.0)
+        self._lens = (aa, radius, d)
+        return True
+
+    def _lens_cameras(self, cam, n: int) -> np.ndarray:
+        from .host import camera_sequence
+        aa, radius, focus = self._lens
+        return camera_sequence(cam, self.width, self.height, self.frame_count, n, aa, radius,
+                               focus if (radius > 0 and focus is not None) else 0.0)
 
     def frame(self, redraw: bool = False, band: int = 1, n_shards: int = 1, shard: int = 0):
         if redraw:                                   # main.cpp:592-596
@@ -93,7 +130,10 @@ class InteractiveSession:
             depth = self.max_bounce_depth
         cam = self.camera.uniforms()
         self.pt.set_frame(self.width, self.height, cam, depth)
-        self.pt.render(self.frame_count, 1, band, n_shards, shard)   # main.cpp:612-613
+        if self._lens is not None and not redraw:
+            self.pt.render_cameras(self.frame_count, self._lens_cameras(cam, 1), band, n_shards, shard)
+        else:
+            self.pt.render(self.frame_count, 1, band, n_shards, shard)   # main.cpp:612-613
         self._rendered_camera = cam
         if not redraw:                               # main.cpp:628
             self.frame_count += 1
@@ -164,10 +204,21 @@ class InteractiveSession:
         """``n`` frames for every pixel, each blended at the weight of the pixel's own frame
         count (one ``PathTracer.render_adaptive`` call with every pixel active): what
         continues a reprojected image, whose pixels hold different counts.  Enables the
-        sample moments itself and advances ``frame_count`` by ``n``."""
+        sample moments itself and advances ``frame_count`` by ``n``.  With ``set_lens`` the
+        frames are ``render_cameras``'s instead: frame ``frame_count + k`` with its camera of
+        the sequence, blended at the weight of that frame number (the statistics then
+        report every pixel active and the call's batch plan)."""
         self.pt.enable_moments(True)
         cam = self.camera.uniforms()
         self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
+        if self._lens is not None:
+            self.pt.render_cameras(self.frame_count, self._lens_cameras(cam, n))
+            plan = self.pt.cameras_batch_plan(n)
+            npix, ntiles = self.width * self.height, ((self.width + 7) // 8) * ((self.height + 7) // 8)
+            self._rendered_camera = cam
+            self.frame_count += n
+            return {"n_pixels": npix, "n_active_pixels": npix, "n_tiles": ntiles, "n_active_tiles": ntiles,
+                    "frames_per_batch": plan["frames_per_batch"], "n_batches": plan["n_batches"]}
         stats = self.pt.render_adaptive(self.frame_count, n, 0.0, 0xFFFFFFFF)
         self._rendered_camera = cam
         self.frame_count += n

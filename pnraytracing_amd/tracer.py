@@ -203,6 +203,32 @@ class PathTracer:
                                            ctypes.byref(nb), ctypes.byref(by)), "pnrt_batch_plan")
         return {"frames_per_batch": fpb.value, "n_batches": nb.value, "batch_bytes": by.value}
 
+    def render_cameras(self, first_frame: int, cameras, band: int = 1, n_shards: int = 1, shard: int = 0):
+        """``render`` with a camera per frame (pnrt_render_cameras): frame ``first_frame + k``
+        is rendered with ``cameras[k]`` -- an (n, 12) or (n, 4, 3) float32 array of eye,
+        lower_left, horizontal, vertical (``host.camera_sequence`` makes one for a pixel
+        filter and a lens) -- in place of ``set_frame``'s camera, which stays current for
+        every other call.  Asynchronous; the array is copied during the call."""
+        cams = np.asarray(cameras)
+        if cams.dtype != np.float32 or cams.ndim not in (2, 3) or cams.shape[1:] not in ((12,), (4, 3)):
+            raise ValueError("render_cameras: cameras must be an (n, 12) or (n, 4, 3) float32 array")
+        cams = np.ascontiguousarray(cams).reshape(-1, 12)
+        if not 0 <= first_frame <= 0xFFFFFFFF:
+            raise ValueError(f"render_cameras: first_frame = {first_frame} is outside 0 .. 2**32 - 1")
+        self._ck(self._lib.pnrt_render_cameras(self._ctx, first_frame, len(cams),
+                                               ctypes.cast(cams.ctypes.data, ctypes.POINTER(N.Camera)) if len(cams) else None,
+                                               band, n_shards, shard), "pnrt_render_cameras")
+
+    def cameras_batch_plan(self, n_frames: int, band: int = 1, n_shards: int = 1, shard: int = 0) -> dict:
+        """``batch_plan`` for a ``render_cameras`` call (pnrt_cameras_batch_plan): the same
+        rules with the 48-byte camera-ray record per path counted in ``batch_bytes``."""
+        if not 0 <= n_frames <= 0xFFFFFFFF:
+            raise ValueError(f"cameras_batch_plan: n_frames = {n_frames} is outside 0 .. 2**32 - 1")
+        fpb, nb, by = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int64()
+        self._ck(self._lib.pnrt_cameras_batch_plan(self._ctx, n_frames, band, n_shards, shard, ctypes.byref(fpb),
+                                                   ctypes.byref(nb), ctypes.byref(by)), "pnrt_cameras_batch_plan")
+        return {"frames_per_batch": fpb.value, "n_batches": nb.value, "batch_bytes": by.value}
+
     def reset_accum(self):
         self._ck(self._lib.pnrt_reset_accum(self._ctx), "pnrt_reset_accum")
 
