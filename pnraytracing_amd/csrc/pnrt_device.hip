@@ -77,6 +77,55 @@ __global__ void pt_math_kernel(int fn, const float* a, const float* b, float* ou
 // =====================================================================================
 // host side
 // =====================================================================================
+static int set_err(pnrt_ctx* c, int code, const std::string& m);
+static hipError_t sync_all(pnrt_ctx* c);
+#define HIPCHK(ctx, expr)                                                                         \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess)                                                                     \
+            return set_err(ctx, PNRT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
+    } while (0)
+
+namespace {
+// A device allocation (Pinned: a pinned host one) and its capacity in bytes, freed with its
+// owner.  Move-only; reads as the pointer it holds.
+template <class T, bool Pinned = false>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    operator T*() const { return p; }
+    void reset() {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+    // a fresh block of exactly `bytes` in place of the old one, whose readers the caller has waited for
+    hipError_t alloc(size_t bytes, unsigned pinned_flags = hipHostMallocDefault) {
+        reset();
+        const hipError_t e = Pinned ? hipHostMalloc((void**)&p, bytes, pinned_flags) : hipMalloc((void**)&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        else p = nullptr;
+        return e;
+    }
+    // at least `bytes`, kept across calls; *moved: the block is another one now
+    int reserve(pnrt_ctx* c, size_t bytes, bool* moved = nullptr) {
+        if (cap >= bytes) return 0;
+        if (p) (void)sync_all(c);          // the old buffer may still be in use by calls in flight
+        if (moved) *moved = true;
+        HIPCHK(c, alloc(bytes));           // (a failure leaves no buffer and no capacity)
+        return 0;
+    }
+};
+template <class T> using PinnedBuf = DevBuf<T, true>;
+}  // namespace
+
 struct pnrt_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -84,12 +133,12 @@ struct pnrt_ctx {
     std::string err;
     // trace faults (pt_wf.h wf_fault): WF_FAULT_WORDS words in host-mapped memory the
     // kernels write only when a check trips; `faulted` latches until reset_accum
-    uint32_t* fault_host = nullptr;
-    uint32_t* fault_dev = nullptr;
+    PinnedBuf<uint32_t> fault_host;
+    uint32_t* fault_dev = nullptr;         // the device's address of fault_host
     bool faulted = false;
     std::string fault_msg;
     // scene
-    std::vector<void*> scene_allocs;
+    std::vector<DevBuf<void>> scene_allocs;
     DevScene scene{};
     bool has_scene = false;
     int max_depth = 0, n_interior = 0, root_is_leaf = 0;
@@ -101,18 +150,16 @@ struct pnrt_ctx {
     std::vector<int> level_off;            // interior nodes of tree level d are indices level_off[d] .. level_off[d + 1] - 1
     float env_max = 0.f;                   // largest |texel| component of the env image (NaN: a NaN texel)
     // env + textures
-    void* hdr = nullptr;
-    void* rnd = nullptr;
-    void* hdr_q = nullptr;      // footprint records of both (DevScene::hdr_q)
-    void* rnd_q = nullptr;
-    void* tex[PT_MAX_TEXTURES] = {};
+    DevBuf<float4> hdr, rnd;
+    DevBuf<float4> hdr_q, rnd_q;    // footprint records of both (DevScene::hdr_q)
+    DevBuf<uint32_t> tex[PT_MAX_TEXTURES];
     int tex_w[PT_MAX_TEXTURES] = {}, tex_h[PT_MAX_TEXTURES] = {};
-    float* unorm8 = nullptr;
+    DevBuf<float> unorm8;
     // frame
     int width = 0, height = 0, max_bounce = 4;
     pnrt_camera cam{};
     bool has_frame = false;
-    float4* accum = nullptr;
+    DevBuf<float4> accum;
     int mode = PNRT_TRAVERSE_ZCULL;
     bool boxes_finite = true;              // every BVH box coordinate finite: z-slab culling allowed (pt_wf.h box_slabs)
     int kernel = 3;                        // 3 = wavefront (default), 1 = v1 one-lane-per-pixel
@@ -143,15 +190,15 @@ struct pnrt_ctx {
         hipEvent_t ev_join = nullptr, ev_blend = nullptr;
         hipEvent_t ev_stage = nullptr;   // WF_STAGGER: the call has reached its drain-heavy end
         bool stage_set = false;
-        float4* primary = nullptr;  size_t primary_cap = 0;
+        DevBuf<float4> primary;
         PrimKey prim;
-        float4* colors = nullptr;   size_t colors_cap = 0;
-        void* wf = nullptr;         size_t wf_cap = 0;
-        uint2* ovf = nullptr;       size_t ovf_cap = 0;
+        DevBuf<float4> colors;
+        DevBuf<char> wf;
+        DevBuf<uint2> ovf;
         bool blend_pending = false;  // ev_blend guards the colour buffer's last reader
         // pnrt_render_cameras: the batch's camera-ray record per path slot and its camera table
-        float4* camrec = nullptr;   size_t camrec_cap = 0;
-        float* camtab = nullptr;    size_t camtab_cap = 0;
+        DevBuf<float4> camrec;
+        DevBuf<float> camtab;
     };
     Pipe pipe[WF_PIPES];
     unsigned n_pipes_small = WF_PIPES;     // pipes small calls rotate over (pipes_init)
@@ -186,49 +233,48 @@ struct pnrt_ctx {
         bool valid = false;
     };
     uint64_t tex_epoch = 1;                // bumped by pnrt_upload_texture (the albedo image reads the textures)
-    float4* aov[PNRT_AOV_COUNT] = {};      size_t aov_cap[PNRT_AOV_COUNT] = {};
+    DevBuf<float4> aov[PNRT_AOV_COUNT];
     GuideKey guide_key;
-    float4* g_primary = nullptr;           size_t g_primary_cap = 0;   // records of the guides' own trace, when no
-    PrimKey g_prim;                                                    // pipe holds the full image's
-    uint2* g_ovf = nullptr;                size_t g_ovf_cap = 0;       // ... and its stack spill area
-    float4* dn_guide = nullptr;            size_t dn_guide_cap = 0;    // compact guide records (pt_denoise.h)
-    float4* dn_img[2] = {};                size_t dn_img_cap[2] = {};  // [0] the denoised image, [1] its ping-pong partner
+    DevBuf<float4> g_primary;              // records of the guides' own trace, when no
+    PrimKey g_prim;                        // pipe holds the full image's
+    DevBuf<uint2> g_ovf;                   // ... and its stack spill area
+    DevBuf<float4> dn_guide;               // compact guide records (pt_denoise.h)
+    DevBuf<float4> dn_img[2];              // [0] the denoised image, [1] its ping-pong partner
     int dn_width = 0, dn_height = 0;       // size of the denoised image (0: none yet)
     // per-pixel sample moments (pnrt_enable_moments; pt_moments.h): none until the first enable
     bool moments_on = false;               // the blends update them
     bool moments_ever = false;             // enabled at least once: the image follows the frame size from then on
-    float4* moments = nullptr;             // width * height records, as the accumulation image
-    float* mom_err = nullptr;              size_t mom_err_cap = 0;     // pnrt_read_error's image
-    MomentsStats* mom_stats = nullptr;     // pnrt_convergence's device record
+    DevBuf<float4> moments;                // width * height records, as the accumulation image
+    DevBuf<float> mom_err;                 // pnrt_read_error's image
+    DevBuf<MomentsStats> mom_stats;        // pnrt_convergence's device record
     // adaptive sampling (pnrt_render_adaptive; pt_adaptive.h): none until the first call
     bool mom_cover = false;                // the moments count every frame the accumulation holds
-    unsigned long long* ad_masks = nullptr;  size_t ad_masks_cap = 0;  // per tile of the selector's rows: activity mask,
-    int* ad_flags = nullptr;               size_t ad_flags_cap = 0;    // "any pixel active" and its exclusive scan
-    int* ad_offs = nullptr;                size_t ad_offs_cap = 0;
-    WfTile* ad_list = nullptr;             size_t ad_list_cap = 0;     // the active-tile list
-    AdaptCounts* ad_counts = nullptr;      // the counts the host reads back
+    DevBuf<unsigned long long> ad_masks;   // per tile of the selector's rows: activity mask,
+    DevBuf<int> ad_flags, ad_offs;         // "any pixel active" and its exclusive scan
+    DevBuf<WfTile> ad_list;                // the active-tile list
+    DevBuf<AdaptCounts> ad_counts;         // the counts the host reads back
     // ray queries (pnrt_query_rays; pt_query.h): none until the first call
-    uint2* q_ovf = nullptr;                size_t q_ovf_cap = 0;       // the query kernel's stack spill area
-    float* q_rays = nullptr;               size_t q_rays_cap = 0;      // the host form's staging buffers: rays in,
-    uint4* q_out = nullptr;                size_t q_out_cap = 0;       // records out
+    DevBuf<uint2> q_ovf;                   // the query kernel's stack spill area
+    DevBuf<float> q_rays;                  // the host form's staging buffers: rays in,
+    DevBuf<uint4> q_out;                   // records out
     // temporal reprojection (pnrt_reproject; pt_reproject.h): none until the first call
-    float4* rp_pos = nullptr;              size_t rp_pos_cap = 0;      // the history: position and normal images of the
-    float4* rp_nrm = nullptr;              size_t rp_nrm_cap = 0;      // view the accumulation was rendered with
-    float4* rp_acc = nullptr;              size_t rp_acc_cap = 0;      // the resampled accumulation and moments, before
-    float4* rp_mom = nullptr;              size_t rp_mom_cap = 0;      // they are copied over the images themselves
-    ReprojectCounts* rp_counts = nullptr;  // the counts the host reads back
+    DevBuf<float4> rp_pos, rp_nrm;         // the history: position and normal images of the view the
+                                           // accumulation was rendered with
+    DevBuf<float4> rp_acc, rp_mom;         // the resampled accumulation and moments, before they are
+                                           // copied over the images themselves
+    DevBuf<ReprojectCounts> rp_counts;     // the counts the host reads back
     // the display transform (pnrt_display; pt_display.h): none until the first call
-    uint32_t* disp = nullptr;              // the RGBA8 display image
+    DevBuf<uint32_t> disp;                 // the RGBA8 display image
     int disp_width = 0, disp_height = 0;   // its size (0: none yet)
-    LumaHist* luma_hist = nullptr;         // pnrt_luma_histogram_read's device record
+    DevBuf<LumaHist> luma_hist;            // pnrt_luma_histogram_read's device record
     // in-place geometry edits (pnrt_update_vertices; pt_refit.h): none until the first call
-    float* rf_stage = nullptr;             size_t rf_stage_cap = 0;    // the host form's staging buffer: vertex records in
-    RefitResult* rf_res = nullptr;         // the root box and the non-finite flag the host reads back
+    DevBuf<float> rf_stage;                // the host form's staging buffer: vertex records in
+    DevBuf<RefitResult> rf_res;            // the root box and the non-finite flag the host reads back
     // per-frame cameras (pnrt_render_cameras; pt_cameras.h): none until the first call.  A call's array is
     // copied into a pinned staging block, from which each batch's table is copied to its pipe in stream
     // order; a block is reused once the event behind its call's last copy has completed
     struct CamStage {
-        float* host = nullptr;  size_t cap = 0;
+        PinnedBuf<float> host;
         hipEvent_t ev = nullptr;
         bool pending = false;
     };
@@ -266,13 +312,6 @@ static int check_fault(pnrt_ctx* c) {
     }
     return c->faulted ? set_err(c, PNRT_E_TRACE, c->fault_msg) : PNRT_OK;
 }
-#define HIPCHK(ctx, expr)                                                                         \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return set_err(ctx, PNRT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
 // Record ev_last after an op queued on c->stream (see pnrt_set_stream).
 static int mark_stream(pnrt_ctx* c) {
     HIPCHK(c, c->ev_last ? hipSuccess : hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming));
@@ -330,23 +369,17 @@ static int prof_collect(pnrt_ctx* c) {
                                  // 80 frames of a quarter / eighth at N = 4 / 8, profiles/r06/h/: +3 to +5 %)
 #endif
 
-static int grow(pnrt_ctx* c, void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return 0;
-    if (*p) {                          // the old buffer may still be in use by calls in flight
-        (void)sync_all(c);
-        (void)hipFree(*p);
-    }
-    *p = nullptr;
-    *cap = 0;
-    HIPCHK(c, hipMalloc(p, bytes));
-    *cap = bytes;
-    return 0;
-}
-
 static void free_scene(pnrt_ctx* c) {
-    for (void* p : c->scene_allocs) (void)hipFree(p);
     c->scene_allocs.clear();
     c->has_scene = false;
+}
+
+// A new block of the scene's, freed with it.
+static hipError_t scene_block(pnrt_ctx* c, size_t bytes, void** p) {
+    c->scene_allocs.emplace_back();
+    const hipError_t e = c->scene_allocs.back().alloc(bytes);
+    *p = c->scene_allocs.back();
+    return e;
 }
 
 template <class T>
@@ -354,8 +387,7 @@ static int upload(pnrt_ctx* c, const std::vector<T>& v, const T** out) {
     void* p = nullptr;
     size_t bytes = v.size() * sizeof(T);
     if (bytes == 0) { *out = nullptr; return 0; }
-    HIPCHK(c, hipMalloc(&p, bytes));
-    c->scene_allocs.push_back(p);
+    HIPCHK(c, scene_block(c, bytes, &p));
     HIPCHK(c, hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice));
     c->scene_bytes += (int64_t)bytes;
     *out = static_cast<const T*>(p);
@@ -664,6 +696,56 @@ static int trace_grid_init(pnrt_ctx* c) {
     return PNRT_OK;
 }
 
+// The per-lane spill area of the trace kernel's stack (LDS holds WF_STACK entries), for a
+// launch of up to the full trace grid (after trace_grid_init).
+struct OvfSize {
+    int stride;
+    size_t bytes;
+};
+static OvfSize ovf_size(const pnrt_ctx* c) {
+    const int stride = c->wf_stack_need > WF_STACK ? c->wf_stack_need - WF_STACK : 1;
+    return {stride, (size_t)c->trace_grid * WF_TRACE_BLOCK * stride * 8};
+}
+
+// The traversal mode the kernels run: z-slab culling only over finite boxes (pnrt_upload_scene).
+static int traverse_mode(const pnrt_ctx* c) { return c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT; }
+
+// A camera's twelve floats -- eye, lower-left corner, horizontal, vertical -- from one form that
+// holds them into another.
+static void cam_floats(float* eye, float* llc, float* hor, float* ver, const float* e, const float* l, const float* h,
+                       const float* v) {
+    std::memcpy(eye, e, 12); std::memcpy(llc, l, 12);
+    std::memcpy(hor, h, 12); std::memcpy(ver, v, 12);
+}
+static void cam_floats(float* eye, float* llc, float* hor, float* ver, const pnrt_camera& cam) {
+    cam_floats(eye, llc, hor, ver, cam.eye, cam.lower_left, cam.horizontal, cam.vertical);
+}
+
+static int shard_rows(int h, int band, int n, int shard) {
+    // 64-bit row positions: band may be any positive int (band >= h: one band), and
+    // shard * band or band * n leave int long before that
+    int64_t rows = 0;
+    const int64_t step = (int64_t)band * n;
+    for (int64_t y0 = (int64_t)shard * band; y0 < h; y0 += step) rows += (h - y0 < band) ? h - y0 : band;
+    return (int)rows;
+}
+
+// The frame parameters of a call that renders frames first .. first + nf - 1 with camera `cam`
+// over a shard selector's rows, in the effective traversal mode.
+static FrameParams frame_params(const pnrt_ctx* c, const pnrt_camera& cam, uint32_t first, uint32_t nf, int band, int nsh,
+                                int shard) {
+    FrameParams fp;
+    cam_floats(fp.eye, fp.llc, fp.hor, fp.ver, cam);
+    fp.width = c->width; fp.height = c->height; fp.max_depth = c->max_bounce;
+    fp.first_frame = first; fp.n_frames = nf;
+    fp.band = band; fp.n_shards = nsh; fp.shard = shard;
+    fp.rows = shard_rows(c->height, band, nsh, shard);
+    fp.mode = traverse_mode(c);
+    return fp;
+}
+// ... and of the whole image (one band, one shard), one frame: the guide images
+static FrameParams full_frame_params(const pnrt_ctx* c, const pnrt_camera& cam) { return frame_params(c, cam, 0, 1, 1, 1, 0); }
+
 // The primary records (camera ray's closest hit per pixel of the shard) depend
 // on the camera, the frame size, the shard, the traversal mode and the scene
 // (scene_epoch: arrays, materials, environment) -- not on the frame number: the
@@ -672,12 +754,19 @@ static int trace_grid_init(pnrt_ctx* c) {
 static pnrt_ctx::PrimKey prim_key(const pnrt_ctx* c, const FrameParams& fp) {
     pnrt_ctx::PrimKey key;
     key.epoch = c->scene_epoch;
-    std::memcpy(key.cam, fp.eye, 12); std::memcpy(key.cam + 3, fp.llc, 12);
-    std::memcpy(key.cam + 6, fp.hor, 12); std::memcpy(key.cam + 9, fp.ver, 12);
+    cam_floats(key.cam, key.cam + 3, key.cam + 6, key.cam + 9, fp.eye, fp.llc, fp.hor, fp.ver);
     key.width = fp.width; key.height = fp.height; key.rows = fp.rows;
     key.band = fp.band; key.n_shards = fp.n_shards; key.shard = fp.shard; key.mode = fp.mode;
     key.valid = true;
     return key;
+}
+// `have` names the records `want` asks for.  any_band: whatever band they were traced with
+// (the same rows in the same order when one shard owns them all).
+static bool prim_key_eq(const pnrt_ctx::PrimKey& have, const pnrt_ctx::PrimKey& want, bool any_band = false) {
+    return have.valid && have.epoch == want.epoch && !std::memcmp(have.cam, want.cam, sizeof want.cam) &&
+           have.width == want.width && have.height == want.height && have.rows == want.rows &&
+           (any_band || have.band == want.band) && have.n_shards == want.n_shards && have.shard == want.shard &&
+           have.mode == want.mode;
 }
 // Ensure `primary` holds the records of fp's shard (render_wavefront's pipes and
 // pnrt_render_guides): traced on stream w -- the trace kernel's step, grid-stride,
@@ -686,11 +775,7 @@ static pnrt_ctx::PrimKey prim_key(const pnrt_ctx* c, const FrameParams& fp) {
 static int ensure_primary(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, hipStream_t w, uint2* ovf, int ovf_stride,
                           float4* primary, pnrt_ctx::PrimKey& have) {
     const pnrt_ctx::PrimKey key = prim_key(c, fp);
-    const bool prim_hit = have.valid && have.epoch == key.epoch && !std::memcmp(have.cam, key.cam, sizeof key.cam) &&
-                          have.width == key.width && have.height == key.height && have.rows == key.rows &&
-                          have.band == key.band && have.n_shards == key.n_shards && have.shard == key.shard &&
-                          have.mode == key.mode;
-    if (!prim_hit) {
+    if (!prim_key_eq(have, key)) {
         ProfScope ps(c, PNRT_K_PRIMARY, w);
         const size_t pix = (size_t)fp.rows * fp.width;
         WfBufs pb{};
@@ -710,14 +795,12 @@ static int ensure_primary(pnrt_ctx* c, const DevScene& s, const FrameParams& fp,
 // A pipe's buffers for batches of `slots` path slots and `color_bytes` of frame colours
 // over a shard of `pix` pixels (render_wavefront, render_adaptive).
 static int pipe_size(pnrt_ctx* c, pnrt_ctx::Pipe& Q, size_t pix, size_t color_bytes, size_t slots, size_t ovf_bytes) {
-    int rc;
-    const float4* old_primary = Q.primary;
-    if ((rc = grow(c, (void**)&Q.primary, &Q.primary_cap, pix * 48)) ||
-        (rc = grow(c, (void**)&Q.colors, &Q.colors_cap, color_bytes)) ||
-        (rc = grow(c, &Q.wf, &Q.wf_cap, wf_bytes(slots) + 512)) ||
-        (rc = grow(c, (void**)&Q.ovf, &Q.ovf_cap, ovf_bytes)))
+    bool moved = false;
+    int rc = Q.primary.reserve(c, pix * 48, &moved);
+    if (moved) Q.prim.valid = false;
+    if (rc || (rc = Q.colors.reserve(c, color_bytes)) || (rc = Q.wf.reserve(c, wf_bytes(slots) + 512)) ||
+        (rc = Q.ovf.reserve(c, ovf_bytes)))
         return rc;
-    if (Q.primary != old_primary) Q.prim.valid = false;
     return PNRT_OK;
 }
 
@@ -843,18 +926,16 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
     c->last_pipe = pi;
     pnrt_ctx::Pipe& P = c->pipe[pi];
     if ((rc = trace_grid_init(c))) return rc;
-    // per-lane spill area of the trace kernel's stack: LDS holds WF_STACK entries
-    const int ovf_stride = c->wf_stack_need > WF_STACK ? c->wf_stack_need - WF_STACK : 1;
-    const size_t ovf_bytes = (size_t)c->trace_grid * WF_TRACE_BLOCK * ovf_stride * 8;
+    const OvfSize ovf = ovf_size(c);
     // every buffer set this call size rotates over is sized now, so no later call of
     // the same size reallocates (a reallocation waits for all calls in flight)
     for (unsigned q = 0; q < npipes; ++q)
-        if ((rc = pipe_size(c, c->pipe[(pi + q) % npipes], pix, pix * 16 * chunk, per_frame * chunk, ovf_bytes))) return rc;
+        if ((rc = pipe_size(c, c->pipe[(pi + q) % npipes], pix, pix * 16 * chunk, per_frame * chunk, ovf.bytes))) return rc;
     if (cams)
         for (unsigned q = 0; q < npipes; ++q) {
             pnrt_ctx::Pipe& Q = c->pipe[(pi + q) % npipes];
-            if ((rc = grow(c, (void**)&Q.camrec, &Q.camrec_cap, per_frame * chunk * CAM_REC_BYTES)) ||
-                (rc = grow(c, (void**)&Q.camtab, &Q.camtab_cap, (size_t)WF_MAX_CHUNK_FRAMES * 48)))
+            if ((rc = Q.camrec.reserve(c, per_frame * chunk * CAM_REC_BYTES)) ||
+                (rc = Q.camtab.reserve(c, (size_t)WF_MAX_CHUNK_FRAMES * 48)))
                 return rc;
         }
     ++c->ncall;
@@ -871,8 +952,8 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
         HIPCHK(c, hipStreamWaitEvent(w, c->pipe[prev_pipe].ev_stage, 0));
     P.stage_set = false;
     // the pipe's primary records: traced now, or still valid from an earlier call (PrimKey)
-    if (!cams && (rc = ensure_primary(c, s, fp, w, P.ovf, ovf_stride, P.primary, P.prim))) return rc;
-    const BatchRoute R = {w, alone, one, stagger, ovf_stride, tiles_x, nullptr, cams};
+    if (!cams && (rc = ensure_primary(c, s, fp, w, P.ovf, ovf.stride, P.primary, P.prim))) return rc;
+    const BatchRoute R = {w, alone, one, stagger, ovf.stride, tiles_x, nullptr, cams};
     if ((rc = run_batches(c, s, fp, P, R, per_frame, chunk, first, nf))) return rc;
     if (cams) {                 // behind the call's last table copy: the staging block is free once it completes
         pnrt_ctx::CamStage& S = c->cam_stage.back();
@@ -894,30 +975,27 @@ static int render_adaptive(pnrt_ctx* c, const DevScene& s, const FrameParams& fp
     const bool alone = !c->serial;
     pnrt_ctx::Pipe& P = c->pipe[c->last_pipe < c->n_pipes_small ? c->last_pipe : 0];
     c->last_pipe = (unsigned)(&P - c->pipe);
-    const int ovf_stride = c->wf_stack_need > WF_STACK ? c->wf_stack_need - WF_STACK : 1;
-    const size_t ovf_bytes = (size_t)c->trace_grid * WF_TRACE_BLOCK * ovf_stride * 8;
-    if ((rc = pipe_size(c, P, pix, per_frame * 16 * chunk, per_frame * chunk, ovf_bytes))) return rc;
+    const OvfSize ovf = ovf_size(c);
+    if ((rc = pipe_size(c, P, pix, per_frame * 16 * chunk, per_frame * chunk, ovf.bytes))) return rc;
     ++c->ncall;
     hipStream_t w = (alone && WF_ALONE_ON_CALLER) ? c->stream : P.w;
     P.stage_set = false;
-    if ((rc = ensure_primary(c, s, fp, w, P.ovf, ovf_stride, P.primary, P.prim))) return rc;
-    const BatchRoute R = {w, alone, c->serial, false, ovf_stride, (c->width + 7) / 8, &ad, nullptr};
+    if ((rc = ensure_primary(c, s, fp, w, P.ovf, ovf.stride, P.primary, P.prim))) return rc;
+    const BatchRoute R = {w, alone, c->serial, false, ovf.stride, (c->width + 7) / 8, &ad, nullptr};
     return run_batches(c, s, fp, P, R, per_frame, chunk, first, nf);
 }
-
-static void free_env(pnrt_ctx* c);
 
 // The scene as the kernels take it: the uploaded arrays with the environment,
 // the textures and the fault words bound now.
 static DevScene launch_scene(const pnrt_ctx* c) {
     DevScene s = c->scene;
-    s.hdr = static_cast<const float4*>(c->hdr);
-    s.rnd = static_cast<const float4*>(c->rnd);
-    s.hdr_q = static_cast<const float4*>(c->hdr_q);
-    s.rnd_q = static_cast<const float4*>(c->rnd_q);
+    s.hdr = c->hdr;
+    s.rnd = c->rnd;
+    s.hdr_q = c->hdr_q;
+    s.rnd_q = c->rnd_q;
     s.n_tex = PT_MAX_TEXTURES;
     for (int i = 0; i < PT_MAX_TEXTURES; ++i) {
-        s.tex[i] = static_cast<const uint32_t*>(c->tex[i]);
+        s.tex[i] = c->tex[i];
         s.tex_w[i] = c->tex_w[i]; s.tex_h[i] = c->tex_h[i];
     }
     s.unorm8 = c->unorm8;
@@ -927,28 +1005,14 @@ static DevScene launch_scene(const pnrt_ctx* c) {
 }
 
 // ---- guide images and the denoised preview -------------------------------------------------
-// Camera `cam` and the effective traversal mode of the current frame, as FrameParams
-// of the whole image (one band, one shard).
-static FrameParams full_frame_params(const pnrt_ctx* c, const pnrt_camera& cam) {
-    FrameParams fp;
-    std::memcpy(fp.eye, cam.eye, 12); std::memcpy(fp.llc, cam.lower_left, 12);
-    std::memcpy(fp.hor, cam.horizontal, 12); std::memcpy(fp.ver, cam.vertical, 12);
-    fp.width = c->width; fp.height = c->height; fp.max_depth = c->max_bounce;
-    fp.first_frame = 0; fp.n_frames = 1;
-    fp.band = 1; fp.n_shards = 1; fp.shard = 0;
-    fp.rows = c->height;
-    fp.mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
-    return fp;
-}
 // What guide images rendered now for camera `cam` would be rendered for.
 static pnrt_ctx::GuideKey guide_key_for(const pnrt_ctx* c, const pnrt_camera& cam) {
     pnrt_ctx::GuideKey k;
     k.epoch = c->scene_epoch;
     k.tex_epoch = c->tex_epoch;
-    std::memcpy(k.cam, cam.eye, 12); std::memcpy(k.cam + 3, cam.lower_left, 12);
-    std::memcpy(k.cam + 6, cam.horizontal, 12); std::memcpy(k.cam + 9, cam.vertical, 12);
+    cam_floats(k.cam, k.cam + 3, k.cam + 6, k.cam + 9, cam);
     k.width = c->width; k.height = c->height;
-    k.mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
+    k.mode = traverse_mode(c);
     k.valid = true;
     return k;
 }
@@ -969,35 +1033,29 @@ static int render_guides(pnrt_ctx* c, const pnrt_camera& cam) {
     const size_t pix = (size_t)c->width * c->height;
     if (pix > 0xFFFFFFFFull / 64) return set_err(c, PNRT_E_ARG, "render_guides: frame too large");
     for (int k = 0; k < PNRT_AOV_COUNT; ++k)
-        if ((rc = grow(c, (void**)&c->aov[k], &c->aov_cap[k], pix * 16))) return rc;
+        if ((rc = c->aov[k].reserve(c, pix * 16))) return rc;
     // A pipe that holds the records of the whole image (any band: one shard owns
     // every row, in row order) for this camera, scene and mode lends them, read-only.
     // Its worker wrote them before the call's blend, which the context stream has
     // waited for; the pipe's next call waits for ev_blend before it may retrace
     // them, so the event is recorded again behind the kernel that reads them here.
-    pnrt_ctx::PrimKey want = prim_key(c, fp);
+    const pnrt_ctx::PrimKey want = prim_key(c, fp);    // one shard of one band: shard 0 of 1
     pnrt_ctx::Pipe* lender = nullptr;
-    for (auto& Q : c->pipe) {
-        const pnrt_ctx::PrimKey& h = Q.prim;
-        if (Q.primary && Q.blend_pending && h.valid && h.epoch == want.epoch && !std::memcmp(h.cam, want.cam, sizeof want.cam) &&
-            h.width == want.width && h.height == want.height && h.rows == want.rows && h.n_shards == 1 && h.shard == 0 &&
-            h.mode == want.mode) {
+    for (auto& Q : c->pipe)
+        if (Q.primary && Q.blend_pending && prim_key_eq(Q.prim, want, /* any_band */ true)) {
             lender = &Q;
             break;
         }
-    }
     const float4* rec = nullptr;
     if (lender) {
         rec = lender->primary;
     } else {            // records of the guides' own, in a buffer and a spill area no pipe uses
-        const int ovf_stride = c->wf_stack_need > WF_STACK ? c->wf_stack_need - WF_STACK : 1;
-        const size_t ovf_bytes = (size_t)c->trace_grid * WF_TRACE_BLOCK * ovf_stride * 8;
-        const float4* old = c->g_primary;
-        if ((rc = grow(c, (void**)&c->g_primary, &c->g_primary_cap, pix * 48)) ||
-            (rc = grow(c, (void**)&c->g_ovf, &c->g_ovf_cap, ovf_bytes)))
-            return rc;
-        if (c->g_primary != old) c->g_prim.valid = false;
-        if ((rc = ensure_primary(c, s, fp, c->stream, c->g_ovf, ovf_stride, c->g_primary, c->g_prim))) return rc;
+        const OvfSize ovf = ovf_size(c);
+        bool moved = false;
+        rc = c->g_primary.reserve(c, pix * 48, &moved);
+        if (moved) c->g_prim.valid = false;
+        if (rc || (rc = c->g_ovf.reserve(c, ovf.bytes))) return rc;
+        if ((rc = ensure_primary(c, s, fp, c->stream, c->g_ovf, ovf.stride, c->g_primary, c->g_prim))) return rc;
         rec = c->g_primary;
     }
     hipLaunchKernelGGL(pt_guides, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, s, rec,
@@ -1020,14 +1078,13 @@ static int query_launch(pnrt_ctx* c, const float* rays, int64_t n, int kind, uin
     int rc;
     if ((rc = trace_grid_init(c))) return rc;
     const DevScene s = launch_scene(c);
-    const int ovf_stride = c->wf_stack_need > WF_STACK ? c->wf_stack_need - WF_STACK : 1;
-    const size_t ovf_bytes = (size_t)c->trace_grid * WF_TRACE_BLOCK * ovf_stride * 8;
-    if ((rc = grow(c, (void**)&c->q_ovf, &c->q_ovf_cap, ovf_bytes))) return rc;
+    const OvfSize ovf = ovf_size(c);
+    if ((rc = c->q_ovf.reserve(c, ovf.bytes))) return rc;
     WfBufs qb{};
     qb.ovf = c->q_ovf;
     qb.fault = c->fault_dev;
-    qb.ovf_stride = (uint32_t)ovf_stride;
-    const int mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
+    qb.ovf_stride = (uint32_t)ovf.stride;
+    const int mode = traverse_mode(c);
     const int any = kind == PNRT_QUERY_ANY;
     for (int64_t at = 0; at < n; at += QUERY_MAX_LAUNCH) {
         const uint32_t m = (uint32_t)std::min<int64_t>(n - at, QUERY_MAX_LAUNCH);
@@ -1057,16 +1114,23 @@ static int query_check(pnrt_ctx* c, const void* rays, int64_t n, int kind, const
     return PNRT_OK;
 }
 
-static int denoise(pnrt_ctx* c, const pnrt_denoise_params& p) {
+// The images both denoisers filter in and their launch grid: the compact guide records and
+// the ping-pong pair.
+static int denoise_reserve(pnrt_ctx* c, dim3* grid) {
     int rc;
     const size_t pix = (size_t)c->width * c->height;
-    if ((rc = grow(c, (void**)&c->dn_guide, &c->dn_guide_cap, pix * 32)) ||
-        (rc = grow(c, (void**)&c->dn_img[0], &c->dn_img_cap[0], pix * 16)) ||
-        (rc = grow(c, (void**)&c->dn_img[1], &c->dn_img_cap[1], pix * 16)))
+    if ((rc = c->dn_guide.reserve(c, pix * 32)) || (rc = c->dn_img[0].reserve(c, pix * 16)) ||
+        (rc = c->dn_img[1].reserve(c, pix * 16)))
         return rc;
+    *grid = dim3((unsigned)((c->width + 15) / 16), (unsigned)((c->height + 15) / 16));
+    return PNRT_OK;
+}
+
+static int denoise(pnrt_ctx* c, const pnrt_denoise_params& p) {
+    dim3 grid;
+    if (int rc = denoise_reserve(c, &grid)) return rc;
     DenoiseParams d{};
     d.width = c->width; d.height = c->height;
-    const dim3 grid((unsigned)((c->width + 15) / 16), (unsigned)((c->height + 15) / 16));
     // level i reads image (first + i) & 1 and writes the other, so the last one writes dn_img[0]
     const int first = p.levels & 1;
     hipLaunchKernelGGL(pt_denoise_prep, grid, dim3(256), 0, c->stream, d, c->scene.materials, c->scene.n_materials,
@@ -1099,18 +1163,13 @@ static int denoise(pnrt_ctx* c, const pnrt_denoise_params& p) {
 
 // pnrt_denoise_variance: the same images and ping-pong as denoise(), the kernels of pt_denoise_var.h
 static int denoise_variance(pnrt_ctx* c, const pnrt_denoise_variance_params& p) {
-    int rc;
-    const size_t pix = (size_t)c->width * c->height;
-    if ((rc = grow(c, (void**)&c->dn_guide, &c->dn_guide_cap, pix * 32)) ||
-        (rc = grow(c, (void**)&c->dn_img[0], &c->dn_img_cap[0], pix * 16)) ||
-        (rc = grow(c, (void**)&c->dn_img[1], &c->dn_img_cap[1], pix * 16)))
-        return rc;
+    dim3 grid;
+    if (int rc = denoise_reserve(c, &grid)) return rc;
     DenoiseVarParams d{};
     d.width = c->width; d.height = c->height;
     d.sigma_v = p.sigma_variance;
     d.inv_n = 1.0f / (p.sigma_normal * p.sigma_normal);
     d.inv_p = 1.0f / (p.sigma_position * p.sigma_position);
-    const dim3 grid((unsigned)((c->width + 15) / 16), (unsigned)((c->height + 15) / 16));
     const int first = p.levels & 1;      // the last pass writes dn_img[0]
     // the moments are written by the blend launches, which this stream has queued before
     hipLaunchKernelGGL(pt_denoise_var_prep, grid, dim3(256), 0, c->stream, d, c->scene.materials, c->scene.n_materials,
@@ -1139,13 +1198,76 @@ static int denoise_variance(pnrt_ctx* c, const pnrt_denoise_variance_params& p) 
 // A zeroed moments image of the current frame size, in place of the old one (the
 // caller has waited for the calls in flight).
 static int moments_alloc(pnrt_ctx* c) {
-    (void)hipFree(c->moments);
-    c->moments = nullptr;
     const size_t bytes = (size_t)c->width * c->height * 16;
-    HIPCHK(c, hipMalloc(&c->moments, bytes));
+    HIPCHK(c, c->moments.alloc(bytes));
     HIPCHK(c, hipMemsetAsync(c->moments, 0, bytes, c->stream));
     c->mom_cover = true;             // first enabled, or zeroed with the accumulation (a resize)
     return mark_stream(c);
+}
+
+// ---- preconditions several entry points share: PNRT_OK, or the error set in `who`'s name -------
+// (The two denoisers keep their own: they ask for the accumulation image and the guide images as
+// well, and tests/test_denoise_variance_api.py reads pnrt_denoise_variance's messages from its body.)
+static int need_scene_frame(pnrt_ctx* c, const char* who) {
+    if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, std::string(who) + ": upload_scene and set_frame first");
+    return PNRT_OK;
+}
+static int check_selector(pnrt_ctx* c, const char* who, int band, int nsh, int shard) {
+    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, std::string(who) + ": bad shard selector");
+    return PNRT_OK;
+}
+// frame 0xFFFFFFFF has the blend weight 1 / (float)0 (frameCount + 1 wraps), and the
+// frames after it would restart at 0: refused before anything is queued
+static int check_frame_range(pnrt_ctx* c, const char* who, uint32_t first, uint32_t nf) {
+    if ((uint64_t)first + nf > 0xFFFFFFFFull)
+        return set_err(c, PNRT_E_ARG, std::string(who) + ": first_frame + n_frames exceeds 0xFFFFFFFF (the last frame number is 0xFFFFFFFE)");
+    return PNRT_OK;
+}
+// there is a moments image to read
+static int need_moments_image(pnrt_ctx* c, const char* who) {
+    if (!c->moments_ever) return set_err(c, PNRT_E_STATE, std::string(who) + ": enable_moments first");
+    if (!c->moments) return set_err(c, PNRT_E_STATE, std::string(who) + ": no frame");
+    return PNRT_OK;
+}
+// the sample moments are enabled and count every frame the accumulation holds
+static int need_moments(pnrt_ctx* c, const char* who) {
+    if (!c->moments_on || !c->moments)
+        return set_err(c, PNRT_E_STATE, std::string(who) + ": the sample moments are not enabled (pnrt_enable_moments(ctx, 1) first)");
+    if (!c->mom_cover)
+        return set_err(c, PNRT_E_STATE, std::string(who) + ": frames were rendered while the moments were disabled, so they do not "
+                                              "cover the accumulation (pnrt_reset_accum first)");
+    return PNRT_OK;
+}
+
+// The tail of the pnrt_read_* calls: `bytes` of a device image to the caller behind everything
+// queued, then the faults of the work that completed.
+static int read_back(pnrt_ctx* c, void* out, const void* src, size_t bytes) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, sync_all(c));
+    return check_fault(c);
+}
+
+// What a new context holds on its device (pnrt_create).  A failure leaves the context as
+// far as it got, for pnrt_destroy.
+static int ctx_init(pnrt_ctx* c) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    c->stream = c->own_stream;
+    // the pipelined renderer's worker streams are created with the context, so
+    // they take hardware queues of their own before the caller creates more streams
+    if (int rc = pipes_init(c)) return rc;
+    void* fd = nullptr;
+    HIPCHK(c, c->fault_host.alloc(256, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(c, hipHostGetDevicePointer(&fd, c->fault_host, 0));
+    std::memset(c->fault_host, 0, 256);
+    c->fault_dev = static_cast<uint32_t*>(fd);
+    HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(c_sobolV), kSobolV, sizeof kSobolV));
+    float lut[256];
+    for (int i = 0; i < 256; ++i) lut[i] = (float)i / 255.0f;   // GL UNORM8 -> float
+    HIPCHK(c, c->unorm8.alloc(sizeof lut));
+    HIPCHK(c, hipMemcpy(c->unorm8, lut, sizeof lut, hipMemcpyHostToDevice));
+    return PNRT_OK;
 }
 
 extern "C" {
@@ -1175,86 +1297,31 @@ int pnrt_create(int device, pnrt_ctx** out) {
     pnrt_ctx* c = new pnrt_ctx();
     c->device = device;
     c->batch_bytes_cap = (size_t)cap;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        return PNRT_E_HIP;
-    }
-    c->stream = c->own_stream;
-    // the pipelined renderer's worker streams are created with the context, so
-    // they take hardware queues of their own before the caller creates more streams
-    if (pipes_init(c) != PNRT_OK) {
-        (void)hipStreamDestroy(c->own_stream);
-        delete c;
-        return PNRT_E_HIP;
-    }
-    void* fh = nullptr;
-    void* fd = nullptr;
-    if (hipHostMalloc(&fh, 256, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer(&fd, fh, 0) != hipSuccess) {
-        if (fh) (void)hipHostFree(fh);
-        (void)hipStreamDestroy(c->own_stream);
-        delete c;
-        return PNRT_E_HIP;
-    }
-    std::memset(fh, 0, 256);
-    c->fault_host = static_cast<uint32_t*>(fh);
-    c->fault_dev = static_cast<uint32_t*>(fd);
-    if (hipMemcpyToSymbol(HIP_SYMBOL(c_sobolV), kSobolV, sizeof kSobolV) != hipSuccess) {
-        (void)hipStreamDestroy(c->own_stream);
-        delete c;
-        return PNRT_E_HIP;
-    }
-    float lut[256];
-    for (int i = 0; i < 256; ++i) lut[i] = (float)i / 255.0f;   // GL UNORM8 -> float
-    if (hipMalloc(&c->unorm8, sizeof lut) != hipSuccess ||
-        hipMemcpy(c->unorm8, lut, sizeof lut, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipStreamDestroy(c->own_stream);
-        delete c;
+    if (ctx_init(c) != PNRT_OK) {
+        pnrt_destroy(c);
         return PNRT_E_HIP;
     }
     *out = c;
     return PNRT_OK;
 }
 
+// The streams and events are destroyed here, and only here; the buffers go with the context.
+// (Also pnrt_create's failure path: any of the streams and events may not exist yet.)
 void pnrt_destroy(pnrt_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    (void)sync_all(c);
-    free_scene(c);
-    free_env(c);
-    for (void* t : c->tex) (void)hipFree(t);
-    (void)hipFree(c->unorm8);
-    (void)hipFree(c->accum);
-    (void)sync_all(c);
+    if (c->stream) (void)sync_all(c);
     for (auto& P : c->pipe) {
-        (void)hipFree(P.primary); (void)hipFree(P.colors); (void)hipFree(P.wf); (void)hipFree(P.ovf);
-        (void)hipFree(P.camrec); (void)hipFree(P.camtab);
         if (P.w) (void)hipStreamDestroy(P.w);
-        if (P.ev_join) (void)hipEventDestroy(P.ev_join);
-        if (P.ev_blend) (void)hipEventDestroy(P.ev_blend);
-        if (P.ev_stage) (void)hipEventDestroy(P.ev_stage);
+        for (hipEvent_t e : {P.ev_join, P.ev_blend, P.ev_stage})
+            if (e) (void)hipEventDestroy(e);
     }
-    for (float4* a : c->aov) (void)hipFree(a);
-    (void)hipFree(c->g_primary); (void)hipFree(c->g_ovf); (void)hipFree(c->dn_guide);
-    (void)hipFree(c->dn_img[0]); (void)hipFree(c->dn_img[1]);
-    (void)hipFree(c->moments); (void)hipFree(c->mom_err); (void)hipFree(c->mom_stats);
-    (void)hipFree(c->ad_masks); (void)hipFree(c->ad_flags); (void)hipFree(c->ad_offs); (void)hipFree(c->ad_list);
-    (void)hipFree(c->ad_counts);
-    (void)hipFree(c->q_ovf); (void)hipFree(c->q_rays); (void)hipFree(c->q_out);
-    (void)hipFree(c->rp_pos); (void)hipFree(c->rp_nrm); (void)hipFree(c->rp_acc); (void)hipFree(c->rp_mom);
-    (void)hipFree(c->rp_counts);
-    (void)hipFree(c->disp); (void)hipFree(c->luma_hist);
-    (void)hipFree(c->rf_stage); (void)hipFree(c->rf_res);
-    for (auto& S : c->cam_stage) {
-        if (S.host) (void)hipHostFree(S.host);
+    for (auto& S : c->cam_stage)
         if (S.ev) (void)hipEventDestroy(S.ev);
-    }
-
     for (auto& p : c->ev_pending) { c->ev_pool.push_back(p.second.first); c->ev_pool.push_back(p.second.second); }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->ev_last) (void)hipEventDestroy(c->ev_last);
-    if (c->fault_host) (void)hipHostFree(c->fault_host);
-    (void)hipStreamDestroy(c->own_stream);
+    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
 
@@ -1353,10 +1420,8 @@ int pnrt_upload_scene(pnrt_ctx* c, const float* V, int nv, const float* M, int n
         float4 a, b, d;
         a.x = p0[0]; a.y = p0[1]; a.z = p0[2]; a.w = p1[0];
         b.x = p1[1]; b.y = p1[2]; b.z = p2[0]; b.w = p2[1];
-        int mb, tb; std::memcpy(&mb, &mat, 4); std::memcpy(&tb, &tex, 4);
         d.x = p2[2];
         std::memcpy(&d.y, &mat, 4); std::memcpy(&d.z, &tex, 4); d.w = 0.f;
-        (void)mb; (void)tb;
         tris[3 * (size_t)i] = a; tris[3 * (size_t)i + 1] = b; tris[3 * (size_t)i + 2] = d;
         tidx[i] = make_int4(id[0], id[1], id[2], 0);
     }
@@ -1495,8 +1560,7 @@ int pnrt_upload_scene(pnrt_ctx* c, const float* V, int nv, const float* M, int n
         if (nb + tb >= ((size_t)1 << 32) - 64)
             return set_err(c, PNRT_E_SCENE, "scene too large: nodes + triangles must stay below 4 GiB");
         void* g = nullptr;
-        HIPCHK(c, hipMalloc(&g, nb + tb));
-        c->scene_allocs.push_back(g);
+        HIPCHK(c, scene_block(c, nb + tb, &g));
         if (nb) HIPCHK(c, hipMemcpy(g, nodes.data(), nb, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(static_cast<char*>(g) + nb, tris.data(), tb, hipMemcpyHostToDevice));
         c->scene_bytes += (int64_t)(nb + tb);
@@ -1605,9 +1669,8 @@ static int update_vertices(pnrt_ctx* c, const char* who, int first, int count, c
     HIPCHK(c, sync_all(c));
     if (count > 0) {
         int rc;
-        if (!c->rf_res) HIPCHK(c, hipMalloc(&c->rf_res, sizeof(RefitResult)));
-        if (src_host && (rc = grow(c, (void**)&c->rf_stage, &c->rf_stage_cap, (size_t)std::min(count, REFIT_MAX_STAGE) * 60)))
-            return rc;
+        if ((rc = c->rf_res.reserve(c, sizeof(RefitResult)))) return rc;
+        if (src_host && (rc = c->rf_stage.reserve(c, (size_t)std::min(count, REFIT_MAX_STAGE) * 60))) return rc;
         hipStream_t st = c->stream;
         RefitResult res0{};
         for (int k = 0; k < 3; ++k) { res0.root[k] = s.root_min[k]; res0.root[3 + k] = s.root_max[k]; }
@@ -1730,9 +1793,7 @@ int pnrt_upload_texture(pnrt_ctx* c, int slot, const uint8_t* px, int w, int h, 
             texels[(size_t)j * w + i] = rgb[0] | (rgb[1] << 8) | (rgb[2] << 16);
         }
     HIPCHK(c, sync_all(c));             // pipelined calls may still sample the old texture
-    (void)hipFree(c->tex[slot]);
-    c->tex[slot] = nullptr;
-    HIPCHK(c, hipMalloc(&c->tex[slot], texels.size() * 4));
+    HIPCHK(c, c->tex[slot].alloc(texels.size() * 4));
     HIPCHK(c, hipMemcpy(c->tex[slot], texels.data(), texels.size() * 4, hipMemcpyHostToDevice));
     c->tex_w[slot] = w; c->tex_h[slot] = h;
     ++c->tex_epoch;                      // the albedo guide image samples the textures
@@ -1756,42 +1817,39 @@ __global__ void env_quad_kernel(const float4* img, int w, int h, float4* q) {
 }
 
 static void free_env(pnrt_ctx* c) {
-    (void)hipFree(c->hdr); (void)hipFree(c->rnd); (void)hipFree(c->hdr_q); (void)hipFree(c->rnd_q);
-    c->hdr = c->rnd = c->hdr_q = c->rnd_q = nullptr;
+    c->hdr.reset(); c->rnd.reset(); c->hdr_q.reset(); c->rnd_q.reset();
 }
 
-static int env_quads(pnrt_ctx* c, int w, int h) {
-    const size_t n = (size_t)(w + 1) * (h + 1);
-    HIPCHK(c, hipMalloc(&c->hdr_q, n * 64));
-    HIPCHK(c, hipMalloc(&c->rnd_q, n * 64));
-    const unsigned g = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(env_quad_kernel, dim3(g), dim3(256), 0, c->stream, (const float4*)c->hdr, w, h, (float4*)c->hdr_q);
-    hipLaunchKernelGGL(env_quad_kernel, dim3(g), dim3(256), 0, c->stream, (const float4*)c->rnd, w, h, (float4*)c->rnd_q);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PNRT_OK;
-}
-
-int pnrt_upload_env(pnrt_ctx* c, const float* rgb, const float* rnd, int w, int h) {
-    if (!c) return PNRT_E_ARG;
+// The two env uploads begin by dropping the old environment, once the calls in flight have
+// rendered with it ...
+static int env_begin(pnrt_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_all(c));
     free_env(c);
     c->scene.has_hdr = 0;
     set_emit_max(c);
     ++c->scene_epoch;                    // a primary miss records the env colour
-    if (!rgb) return PNRT_OK;
-    if (!rnd || w <= 0 || h <= 0) return set_err(c, PNRT_E_ARG, "upload_env: bad arguments");
-    std::vector<float4> a((size_t)w * h), b((size_t)w * h);
-    for (size_t i = 0; i < a.size(); ++i) {
-        a[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.f);
-        b[i] = make_float4(rnd[3 * i], rnd[3 * i + 1], rnd[3 * i + 2], 0.f);
-    }
-    HIPCHK(c, hipMalloc(&c->hdr, a.size() * 16));
-    HIPCHK(c, hipMalloc(&c->rnd, b.size() * 16));
-    HIPCHK(c, hipMemcpy(c->hdr, a.data(), a.size() * 16, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->rnd, b.data(), b.size() * 16, hipMemcpyHostToDevice));
-    if (int rc = env_quads(c, w, h)) return rc;
+    return PNRT_OK;
+}
+// ... allocate both w x h images and fill hdr with `rgb` ...
+static int env_images(pnrt_ctx* c, const float* rgb, size_t n) {
+    std::vector<float4> a(n);
+    for (size_t i = 0; i < n; ++i) a[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.f);
+    HIPCHK(c, c->hdr.alloc(n * 16));
+    HIPCHK(c, c->rnd.alloc(n * 16));
+    HIPCHK(c, hipMemcpy(c->hdr, a.data(), n * 16, hipMemcpyHostToDevice));
+    return PNRT_OK;
+}
+// ... and finish, with rnd filled too, by the footprint records of both and the scene's env fields.
+static int env_finish(pnrt_ctx* c, const float* rgb, int w, int h) {
+    const size_t n = (size_t)(w + 1) * (h + 1);
+    HIPCHK(c, c->hdr_q.alloc(n * 64));
+    HIPCHK(c, c->rnd_q.alloc(n * 64));
+    const unsigned g = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(env_quad_kernel, dim3(g), dim3(256), 0, c->stream, (const float4*)c->hdr, w, h, (float4*)c->hdr_q);
+    hipLaunchKernelGGL(env_quad_kernel, dim3(g), dim3(256), 0, c->stream, (const float4*)c->rnd, w, h, (float4*)c->rnd_q);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     c->scene.has_hdr = 1;
     c->scene.hdr_w = w; c->scene.hdr_h = h;
     c->env_max = abs_max(rgb, 3 * (size_t)w * h, 0.f);
@@ -1799,24 +1857,28 @@ int pnrt_upload_env(pnrt_ctx* c, const float* rgb, const float* rnd, int w, int 
     return PNRT_OK;
 }
 
+int pnrt_upload_env(pnrt_ctx* c, const float* rgb, const float* rnd, int w, int h) {
+    if (!c) return PNRT_E_ARG;
+    if (int rc = env_begin(c)) return rc;
+    if (!rgb) return PNRT_OK;
+    if (!rnd || w <= 0 || h <= 0) return set_err(c, PNRT_E_ARG, "upload_env: bad arguments");
+    const size_t n = (size_t)w * h;
+    std::vector<float4> b(n);
+    for (size_t i = 0; i < n; ++i) b[i] = make_float4(rnd[3 * i], rnd[3 * i + 1], rnd[3 * i + 2], 0.f);
+    if (int rc = env_images(c, rgb, n)) return rc;
+    HIPCHK(c, hipMemcpy(c->rnd, b.data(), n * 16, hipMemcpyHostToDevice));
+    return env_finish(c, rgb, w, h);
+}
+
 int pnrt_upload_env_build(pnrt_ctx* c, const float* rgb, int w, int h) {
     if (!c) return PNRT_E_ARG;
     if (!rgb || w <= 0 || h <= 0) return set_err(c, PNRT_E_ARG, "upload_env_build: bad arguments");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, sync_all(c));
-    free_env(c);
-    c->scene.has_hdr = 0;
-    set_emit_max(c);
-    ++c->scene_epoch;                    // a primary miss records the env colour
+    if (int rc = env_begin(c)) return rc;
     const size_t n = (size_t)w * h;
-    std::vector<float4> a(n);
-    for (size_t i = 0; i < n; ++i) a[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.f);
-    HIPCHK(c, hipMalloc(&c->hdr, n * 16));
-    HIPCHK(c, hipMalloc(&c->rnd, n * 16));
-    HIPCHK(c, hipMemcpy(c->hdr, a.data(), n * 16, hipMemcpyHostToDevice));
-    float* tmp = nullptr;                     // lumY/pdfY | lumX | cdfY | marginX | cdfX | sum
-    HIPCHK(c, hipMalloc(&tmp, (3 * n + 2 * (size_t)w + 64) * 4));
-    float *pdfY = tmp, *lumX = tmp + n, *cdfY = tmp + 2 * n, *marginX = tmp + 3 * n, *cdfX = marginX + w,
+    if (int rc = env_images(c, rgb, n)) return rc;
+    DevBuf<float> tmp;                        // lumY/pdfY | lumX | cdfY | marginX | cdfX | sum
+    HIPCHK(c, tmp.alloc((3 * n + 2 * (size_t)w + 64) * 4));
+    float *pdfY = tmp.p, *lumX = pdfY + n, *cdfY = pdfY + 2 * n, *marginX = pdfY + 3 * n, *cdfX = marginX + w,
           *sum = cdfX + w;
     const unsigned gp = (unsigned)((n + 255) / 256), gx = (unsigned)((w + 255) / 256);
     hipLaunchKernelGGL(env_lumen_kernel, dim3(gp), dim3(256), 0, c->stream, (const float4*)c->hdr, pdfY, lumX, w, h);
@@ -1825,17 +1887,11 @@ int pnrt_upload_env_build(pnrt_ctx* c, const float* rgb, int w, int h) {
     hipLaunchKernelGGL(env_cdfx_kernel, dim3(1), dim3(64), 0, c->stream, (const float*)marginX, cdfX, w);
     hipLaunchKernelGGL(env_cdfy_kernel, dim3(gx), dim3(256), 0, c->stream, (const float*)pdfY, (const float*)marginX, cdfY, w, h);
     hipLaunchKernelGGL(env_table_kernel, dim3(gp), dim3(256), 0, c->stream, (const float*)cdfX, (const float*)cdfY,
-                       (const float*)pdfY, static_cast<float4*>(c->rnd), w, h);
+                       (const float*)pdfY, c->rnd.p, w, h);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(tmp);
     if (e != hipSuccess) return set_err(c, PNRT_E_HIP, std::string("upload_env_build: ") + hipGetErrorString(e));
-    if (int rc = env_quads(c, w, h)) return rc;
-    c->scene.has_hdr = 1;
-    c->scene.hdr_w = w; c->scene.hdr_h = h;
-    c->env_max = abs_max(rgb, 3 * n, 0.f);
-    set_emit_max(c);
-    return PNRT_OK;
+    return env_finish(c, rgb, w, h);
 }
 
 int pnrt_read_env_table(pnrt_ctx* c, float* out) {
@@ -1857,9 +1913,7 @@ int pnrt_set_frame(pnrt_ctx* c, int w, int h, const pnrt_camera* cam, int depth)
     HIPCHK(c, hipSetDevice(c->device));
     if (w != c->width || h != c->height || !c->accum) {
         HIPCHK(c, sync_all(c));
-        (void)hipFree(c->accum);
-        c->accum = nullptr;
-        HIPCHK(c, hipMalloc(&c->accum, (size_t)w * h * 16));
+        HIPCHK(c, c->accum.alloc((size_t)w * h * 16));
         HIPCHK(c, hipMemsetAsync(c->accum, 0, (size_t)w * h * 16, c->stream));
         c->width = w; c->height = h;
         if (int rc = mark_stream(c)) return rc;
@@ -1872,36 +1926,11 @@ int pnrt_set_frame(pnrt_ctx* c, int w, int h, const pnrt_camera* cam, int depth)
     return PNRT_OK;
 }
 
-static int shard_rows(int h, int band, int n, int shard) {
-    // 64-bit row positions: band may be any positive int (band >= h: one band), and
-    // shard * band or band * n leave int long before that
-    int64_t rows = 0;
-    const int64_t step = (int64_t)band * n;
-    for (int64_t y0 = (int64_t)shard * band; y0 < h; y0 += step) rows += (h - y0 < band) ? h - y0 : band;
-    return (int)rows;
-}
-
-// The frame parameters of a render call over a shard selector's rows.
-static FrameParams call_frame_params(const pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int shard) {
-    FrameParams fp;
-    std::memcpy(fp.eye, c->cam.eye, 12); std::memcpy(fp.llc, c->cam.lower_left, 12);
-    std::memcpy(fp.hor, c->cam.horizontal, 12); std::memcpy(fp.ver, c->cam.vertical, 12);
-    fp.width = c->width; fp.height = c->height; fp.max_depth = c->max_bounce;
-    fp.first_frame = first; fp.n_frames = nf;
-    fp.band = band; fp.n_shards = nsh; fp.shard = shard;
-    fp.rows = shard_rows(c->height, band, nsh, shard);
-    fp.mode = c->boxes_finite ? c->mode : PNRT_TRAVERSE_EXACT;
-    return fp;
-}
-
 int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int shard) {
     if (!c) return PNRT_E_ARG;
-    if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, "render: upload_scene and set_frame first");
-    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "render: bad shard selector");
-    // frame 0xFFFFFFFF has the blend weight 1 / (float)0 (frameCount + 1 wraps), and the
-    // frames after it would restart at 0: refused before anything is queued
-    if ((uint64_t)first + nf > 0xFFFFFFFFull)
-        return set_err(c, PNRT_E_ARG, "render: first_frame + n_frames exceeds 0xFFFFFFFF (the last frame number is 0xFFFFFFFE)");
+    if (int rc = need_scene_frame(c, "render")) return rc;
+    if (int rc = check_selector(c, "render", band, nsh, shard)) return rc;
+    if (int rc = check_frame_range(c, "render", first, nf)) return rc;
     // the one-kernel path keeps its frames in registers: no per-frame colours to take moments of
     if (c->kernel == 1 && c->moments_on)
         return set_err(c, PNRT_E_STATE, "render: PNRT_KERNEL_V1 cannot update the sample moments (pnrt_enable_moments(ctx, 0) first)");
@@ -1909,7 +1938,7 @@ int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int
     if (nf == 0) return PNRT_OK;
     if (!c->moments_on) c->mom_cover = false;    // frames the moments do not count (pnrt_render_adaptive)
     HIPCHK(c, hipSetDevice(c->device));
-    const FrameParams fp = call_frame_params(c, first, nf, band, nsh, shard);
+    const FrameParams fp = frame_params(c, c->cam, first, nf, band, nsh, shard);
     if (fp.rows == 0) return PNRT_OK;
     DevScene s = launch_scene(c);
     if (WF_DIAG_BOUNDS) {                // the bounds check's own test (diagnostic builds only)
@@ -1937,32 +1966,25 @@ static int cam_stage_get(pnrt_ctx* c, size_t bytes) {
         if (!S.pending || hipEventQuery(S.ev) == hipSuccess) at = i;
     }
     if (at == c->cam_stage.size()) {
-        pnrt_ctx::CamStage S;
-        HIPCHK(c, hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-        c->cam_stage.push_back(S);
+        hipEvent_t ev = nullptr;
+        HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        c->cam_stage.emplace_back();
+        c->cam_stage.back().ev = ev;
     }
     std::swap(c->cam_stage[at], c->cam_stage.back());
     pnrt_ctx::CamStage& S = c->cam_stage.back();
     S.pending = false;
-    if (S.cap < bytes) {
-        if (S.host) (void)hipHostFree(S.host);
-        S.host = nullptr; S.cap = 0;
-        const size_t cap = std::max<size_t>(bytes, 4096);
-        HIPCHK(c, hipHostMalloc((void**)&S.host, cap, hipHostMallocDefault));
-        S.cap = cap;
-    }
+    if (S.host.cap < bytes) HIPCHK(c, S.host.alloc(std::max<size_t>(bytes, 4096)));
     return PNRT_OK;
 }
 
 int pnrt_render_cameras(pnrt_ctx* c, uint32_t first, uint32_t nf, const pnrt_camera* cameras, int band, int nsh, int shard) {
     if (!c) return PNRT_E_ARG;
-    if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, "render_cameras: upload_scene and set_frame first");
+    if (int rc = need_scene_frame(c, "render_cameras")) return rc;
     if (c->kernel == 1)
         return set_err(c, PNRT_E_STATE, "render_cameras: PNRT_KERNEL_V1 renders the pnrt_set_frame camera only");
-    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "render_cameras: bad shard selector");
-    if ((uint64_t)first + nf > 0xFFFFFFFFull)
-        return set_err(c, PNRT_E_ARG,
-                       "render_cameras: first_frame + n_frames exceeds 0xFFFFFFFF (the last frame number is 0xFFFFFFFE)");
+    if (int rc = check_selector(c, "render_cameras", band, nsh, shard)) return rc;
+    if (int rc = check_frame_range(c, "render_cameras", first, nf)) return rc;
     if (nf > 0 && !cameras) return set_err(c, PNRT_E_ARG, "render_cameras: cameras is NULL");
     static_assert(sizeof(pnrt_camera) == 48, "twelve floats per camera");
     const float* cf = reinterpret_cast<const float*>(cameras);
@@ -1974,7 +1996,7 @@ int pnrt_render_cameras(pnrt_ctx* c, uint32_t first, uint32_t nf, const pnrt_cam
     if (int rc = check_fault(c)) return rc;      // an earlier call's trace fault (completed work)
     if (nf == 0) return PNRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const FrameParams fp = call_frame_params(c, first, nf, band, nsh, shard);
+    const FrameParams fp = frame_params(c, c->cam, first, nf, band, nsh, shard);
     if (fp.rows == 0) return PNRT_OK;
     if (!c->moments_on) c->mom_cover = false;    // frames the moments do not count, as pnrt_render's
     const DevScene s = launch_scene(c);
@@ -1989,7 +2011,7 @@ static int batch_plan(pnrt_ctx* c, const std::string& who, size_t per_path, uint
                       uint32_t* frames_per_batch, uint32_t* n_batches, int64_t* bytes) {
     if (!c) return PNRT_E_ARG;
     if (!c->has_frame) return set_err(c, PNRT_E_STATE, who + ": set_frame first");
-    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, who + ": bad shard selector");
+    if (int rc = check_selector(c, who.c_str(), band, nsh, shard)) return rc;
     uint32_t chunk = 0, nb = 0;
     int64_t by = 0;
     const int rows = shard_rows(c->height, band, nsh, shard);
@@ -2041,17 +2063,14 @@ int pnrt_reset_accum(pnrt_ctx* c) {
 int pnrt_read_accum(pnrt_ctx* c, float* out) {
     if (!c || !out) return PNRT_E_ARG;
     if (!c->accum) return set_err(c, PNRT_E_STATE, "read_accum: no frame");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->accum, (size_t)c->width * c->height * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, sync_all(c));
-    return check_fault(c);
+    return read_back(c, out, c->accum, (size_t)c->width * c->height * 16);
 }
 
-void* pnrt_accum_device_ptr(pnrt_ctx* c) { return c ? c->accum : nullptr; }
+void* pnrt_accum_device_ptr(pnrt_ctx* c) { return c ? c->accum.p : nullptr; }
 
 int pnrt_render_guides(pnrt_ctx* c) {
     if (!c) return PNRT_E_ARG;
-    if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, "render_guides: upload_scene and set_frame first");
+    if (int rc = need_scene_frame(c, "render_guides")) return rc;
     if (int rc = check_fault(c)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     return render_guides(c, c->cam);
@@ -2063,15 +2082,11 @@ int pnrt_read_aov(pnrt_ctx* c, int which, float* out) {
     if (!c->guide_key.valid || !c->aov[which]) return set_err(c, PNRT_E_STATE, "read_aov: render_guides first");
     if (c->guide_key.width != c->width || c->guide_key.height != c->height)
         return set_err(c, PNRT_E_STATE, "read_aov: the guide images have another size than the frame: render_guides again");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->aov[which], (size_t)c->guide_key.width * c->guide_key.height * 16, hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, sync_all(c));
-    return check_fault(c);
+    return read_back(c, out, c->aov[which], (size_t)c->guide_key.width * c->guide_key.height * 16);
 }
 
 void* pnrt_aov_device_ptr(pnrt_ctx* c, int which) {
-    return (c && which >= 0 && which < PNRT_AOV_COUNT) ? c->aov[which] : nullptr;
+    return (c && which >= 0 && which < PNRT_AOV_COUNT) ? c->aov[which].p : nullptr;
 }
 
 int pnrt_query_rays_device(pnrt_ctx* c, const void* rays, int64_t n, int kind, void* out) {
@@ -2091,9 +2106,7 @@ int pnrt_query_rays(pnrt_ctx* c, const float* rays, int64_t n, int kind, pnrt_hi
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t stage = std::min<int64_t>(n, QUERY_MAX_STAGE);
     int rc;
-    if ((rc = grow(c, (void**)&c->q_rays, &c->q_rays_cap, (size_t)stage * 28)) ||
-        (rc = grow(c, (void**)&c->q_out, &c->q_out_cap, (size_t)stage * 64)))
-        return rc;
+    if ((rc = c->q_rays.reserve(c, (size_t)stage * 28)) || (rc = c->q_out.reserve(c, (size_t)stage * 64))) return rc;
     for (int64_t at = 0; at < n; at += stage) {
         const int64_t m = std::min<int64_t>(n - at, stage);
         HIPCHK(c, hipMemcpyAsync(c->q_rays, rays + 7 * at, (size_t)m * 28, hipMemcpyHostToDevice, c->stream));
@@ -2151,13 +2164,10 @@ int pnrt_read_denoised(pnrt_ctx* c, float* out) {
     if (!c->dn_width || !c->dn_img[0]) return set_err(c, PNRT_E_STATE, "read_denoised: denoise first");
     if (c->dn_width != c->width || c->dn_height != c->height)
         return set_err(c, PNRT_E_STATE, "read_denoised: the denoised image has another size than the frame: denoise again");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->dn_img[0], (size_t)c->width * c->height * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, sync_all(c));
-    return check_fault(c);
+    return read_back(c, out, c->dn_img[0], (size_t)c->width * c->height * 16);
 }
 
-void* pnrt_denoised_device_ptr(pnrt_ctx* c) { return c ? c->dn_img[0] : nullptr; }
+void* pnrt_denoised_device_ptr(pnrt_ctx* c) { return c ? c->dn_img[0].p : nullptr; }
 
 int pnrt_enable_moments(pnrt_ctx* c, int on) {
     if (!c) return PNRT_E_ARG;
@@ -2171,26 +2181,21 @@ int pnrt_enable_moments(pnrt_ctx* c, int on) {
     return PNRT_OK;
 }
 
-void* pnrt_moments_device_ptr(pnrt_ctx* c) { return c ? c->moments : nullptr; }
+void* pnrt_moments_device_ptr(pnrt_ctx* c) { return c ? c->moments.p : nullptr; }
 
 int pnrt_read_moments(pnrt_ctx* c, float* out) {
     if (!c || !out) return PNRT_E_ARG;
-    if (!c->moments_ever) return set_err(c, PNRT_E_STATE, "read_moments: enable_moments first");
-    if (!c->moments) return set_err(c, PNRT_E_STATE, "read_moments: no frame");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->moments, (size_t)c->width * c->height * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, sync_all(c));
-    return check_fault(c);
+    if (int rc = need_moments_image(c, "read_moments")) return rc;
+    return read_back(c, out, c->moments, (size_t)c->width * c->height * 16);
 }
 
 int pnrt_read_error(pnrt_ctx* c, float* out) {
     if (!c || !out) return PNRT_E_ARG;
-    if (!c->moments_ever) return set_err(c, PNRT_E_STATE, "read_error: enable_moments first");
-    if (!c->moments) return set_err(c, PNRT_E_STATE, "read_error: no frame");
+    if (int rc = need_moments_image(c, "read_error")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t pix = (size_t)c->width * c->height;
     if (pix > 0xFFFFFFFFull) return set_err(c, PNRT_E_ARG, "read_error: frame too large");
-    if (int rc = grow(c, (void**)&c->mom_err, &c->mom_err_cap, pix * 4)) return rc;
+    if (int rc = c->mom_err.reserve(c, pix * 4)) return rc;
     hipLaunchKernelGGL(pt_moments_error_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream,
                        (const float4*)c->moments, c->mom_err, (uint32_t)pix);
     HIPCHK(c, hipGetLastError());
@@ -2204,9 +2209,8 @@ int pnrt_convergence(pnrt_ctx* c, float threshold, int band, int nsh, int shard,
     if (!c || !out) return PNRT_E_ARG;
     if (!std::isfinite(threshold) || !(threshold >= 0.0f))
         return set_err(c, PNRT_E_ARG, "convergence: threshold must be finite and >= 0");
-    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "convergence: bad shard selector");
-    if (!c->moments_ever) return set_err(c, PNRT_E_STATE, "convergence: enable_moments first");
-    if (!c->moments) return set_err(c, PNRT_E_STATE, "convergence: no frame");
+    if (int rc = check_selector(c, "convergence", band, nsh, shard)) return rc;
+    if (int rc = need_moments_image(c, "convergence")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     std::memset(out, 0, sizeof *out);
     const int rows = shard_rows(c->height, band, nsh, shard);
@@ -2215,7 +2219,7 @@ int pnrt_convergence(pnrt_ctx* c, float threshold, int band, int nsh, int shard,
     if (total) {
         // the identities of the record's atomics (static: the copy may read it after this call returns)
         static const MomentsStats kIdentity = {0, 0, 0, 0, 0u, 0xFFFFFFFFu, 0u, 0u};
-        if (!c->mom_stats) HIPCHK(c, hipMalloc(&c->mom_stats, sizeof(MomentsStats)));
+        if (int rc = c->mom_stats.reserve(c, sizeof(MomentsStats))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->mom_stats, &kIdentity, sizeof kIdentity, hipMemcpyHostToDevice, c->stream));
         const unsigned grid = (unsigned)std::min<size_t>((total + MOMENTS_REDUCE_BLOCK - 1) / MOMENTS_REDUCE_BLOCK, 2048);
         hipLaunchKernelGGL(pt_moments_reduce_kernel, dim3(grid), dim3(MOMENTS_REDUCE_BLOCK), 0, c->stream,
@@ -2240,24 +2244,18 @@ int pnrt_convergence(pnrt_ctx* c, float threshold, int band, int nsh, int shard,
 int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float threshold, uint32_t min_frames, int band, int nsh,
                          int shard, pnrt_adaptive_stats* out) {
     if (!c) return PNRT_E_ARG;
-    if (!c->has_scene || !c->has_frame)
-        return set_err(c, PNRT_E_STATE, "render_adaptive: upload_scene and set_frame first");
+    if (int rc = need_scene_frame(c, "render_adaptive")) return rc;
     if (!std::isfinite(threshold) || !(threshold >= 0.0f))
         return set_err(c, PNRT_E_ARG, "render_adaptive: threshold must be finite and >= 0");
-    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "render_adaptive: bad shard selector");
-    if ((uint64_t)first + nf > 0xFFFFFFFFull)
-        return set_err(c, PNRT_E_ARG, "render_adaptive: first_frame + n_frames exceeds 0xFFFFFFFF (the last frame number is 0xFFFFFFFE)");
-    if (!c->moments_on || !c->moments)
-        return set_err(c, PNRT_E_STATE, "render_adaptive: the sample moments are not enabled (pnrt_enable_moments(ctx, 1) first)");
-    if (!c->mom_cover)
-        return set_err(c, PNRT_E_STATE, "render_adaptive: frames were rendered while the moments were disabled, so they do not "
-                                        "cover the accumulation (pnrt_reset_accum first)");
+    if (int rc = check_selector(c, "render_adaptive", band, nsh, shard)) return rc;
+    if (int rc = check_frame_range(c, "render_adaptive", first, nf)) return rc;
+    if (int rc = need_moments(c, "render_adaptive")) return rc;
     if (c->kernel == 1) return set_err(c, PNRT_E_STATE, "render_adaptive: PNRT_KERNEL_V1 has no per-frame colours");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_all(c));                      // the predicate reads the moments as every earlier call left them
     if (int rc = check_fault(c)) return rc;
     pnrt_adaptive_stats st{};
-    const FrameParams fp = call_frame_params(c, first, nf, band, nsh, shard);
+    const FrameParams fp = frame_params(c, c->cam, first, nf, band, nsh, shard);
     const int tiles_x = (c->width + 7) / 8;
     const size_t n_tiles = (size_t)tiles_x * (size_t)((fp.rows + 7) / 8);
     st.n_pixels = (int64_t)fp.rows * c->width;
@@ -2266,12 +2264,10 @@ int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float thresho
     if (n_tiles) {
         if (n_tiles > 0x7FFFFFFFull) return set_err(c, PNRT_E_ARG, "render_adaptive: frame too large");
         int rc;
-        if ((rc = grow(c, (void**)&c->ad_masks, &c->ad_masks_cap, n_tiles * 8)) ||
-            (rc = grow(c, (void**)&c->ad_flags, &c->ad_flags_cap, n_tiles * 4)) ||
-            (rc = grow(c, (void**)&c->ad_offs, &c->ad_offs_cap, n_tiles * 4)) ||
-            (rc = grow(c, (void**)&c->ad_list, &c->ad_list_cap, n_tiles * sizeof(WfTile))))
+        if ((rc = c->ad_masks.reserve(c, n_tiles * 8)) || (rc = c->ad_flags.reserve(c, n_tiles * 4)) ||
+            (rc = c->ad_offs.reserve(c, n_tiles * 4)) || (rc = c->ad_list.reserve(c, n_tiles * sizeof(WfTile))) ||
+            (rc = c->ad_counts.reserve(c, sizeof(AdaptCounts))))
             return rc;
-        if (!c->ad_counts) HIPCHK(c, hipMalloc(&c->ad_counts, sizeof(AdaptCounts)));
         // mask -> scan -> scatter, then the call's one synchronisation: the two counts
         const uint32_t m = min_frames > 2u ? min_frames : 2u;
         AdaptCounts cnt{};
@@ -2312,12 +2308,8 @@ int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float thresho
 
 int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_params* params, pnrt_reproject_stats* out) {
     if (!c) return PNRT_E_ARG;
-    if (!c->has_scene || !c->has_frame) return set_err(c, PNRT_E_STATE, "reproject: upload_scene and set_frame first");
-    if (!c->moments_on || !c->moments)
-        return set_err(c, PNRT_E_STATE, "reproject: the sample moments are not enabled (pnrt_enable_moments(ctx, 1) first)");
-    if (!c->mom_cover)
-        return set_err(c, PNRT_E_STATE, "reproject: frames were rendered while the moments were disabled, so they do not "
-                                        "cover the accumulation (pnrt_reset_accum first)");
+    if (int rc = need_scene_frame(c, "reproject")) return rc;
+    if (int rc = need_moments(c, "reproject")) return rc;
     if (c->kernel == 1) return set_err(c, PNRT_E_STATE, "reproject: PNRT_KERNEL_V1 keeps no sample moments");
     if (!from) return set_err(c, PNRT_E_ARG, "reproject: the camera the accumulation was rendered with is NULL");
     for (const float* v : {from->eye, from->lower_left, from->horizontal, from->vertical})
@@ -2337,10 +2329,10 @@ int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_pa
     HIPCHK(c, sync_all(c));                      // the images as every earlier call left them
     int rc;
     if ((rc = check_fault(c))) return rc;
-    if ((rc = grow(c, (void**)&c->rp_pos, &c->rp_pos_cap, pix * 16)) || (rc = grow(c, (void**)&c->rp_nrm, &c->rp_nrm_cap, pix * 16)) ||
-        (rc = grow(c, (void**)&c->rp_acc, &c->rp_acc_cap, pix * 16)) || (rc = grow(c, (void**)&c->rp_mom, &c->rp_mom_cap, pix * 16)))
+    if ((rc = c->rp_pos.reserve(c, pix * 16)) || (rc = c->rp_nrm.reserve(c, pix * 16)) ||
+        (rc = c->rp_acc.reserve(c, pix * 16)) || (rc = c->rp_mom.reserve(c, pix * 16)) ||
+        (rc = c->rp_counts.reserve(c, REPROJECT_SLOTS * sizeof(ReprojectCounts))))
         return rc;
-    if (!c->rp_counts) HIPCHK(c, hipMalloc(&c->rp_counts, REPROJECT_SLOTS * sizeof(ReprojectCounts)));
     // the guide images of `from` (the current ones when they were rendered for it), kept as the history
     if (!guide_key_eq(c->guide_key, guide_key_for(c, *from)))
         if ((rc = render_guides(c, *from))) return rc;
@@ -2351,8 +2343,7 @@ int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_pa
     }
     if ((rc = render_guides(c, c->cam))) return rc;
     ReprojectArgs ra;
-    std::memcpy(ra.eye, from->eye, 12); std::memcpy(ra.llc, from->lower_left, 12);
-    std::memcpy(ra.hor, from->horizontal, 12); std::memcpy(ra.ver, from->vertical, 12);
+    cam_floats(ra.eye, ra.llc, ra.hor, ra.ver, *from);
     ra.normal_min = p.normal_min; ra.position_tolerance = p.position_tolerance; ra.max_history = p.max_history;
     ra.width = c->width; ra.height = c->height;
     ra.tiles_x = (c->width + 7) / 8;
@@ -2421,7 +2412,7 @@ static const float4* display_source(pnrt_ctx* c, const char* what, int source, c
         }
         return c->dn_img[0];
     }
-    return source == PNRT_DISPLAY_EXTERNAL ? static_cast<const float4*>(src_device) : c->accum;
+    return source == PNRT_DISPLAY_EXTERNAL ? static_cast<const float4*>(src_device) : c->accum.p;
 }
 
 int pnrt_display(pnrt_ctx* c, const pnrt_display_params* params) {
@@ -2443,13 +2434,10 @@ int pnrt_display(pnrt_ctx* c, const pnrt_display_params* params) {
     const uint32_t npix = (uint32_t)((size_t)c->width * c->height);
     if (!c->disp || c->disp_width != c->width || c->disp_height != c->height) {
         // the new image before the old one is freed: its pointer differs, and a failure leaves the old one
-        uint32_t* img = nullptr;
-        HIPCHK(c, hipMalloc(&img, (size_t)npix * 4));
-        if (c->disp) {
-            (void)sync_all(c);
-            (void)hipFree(c->disp);
-        }
-        c->disp = img;
+        DevBuf<uint32_t> img;
+        HIPCHK(c, img.alloc((size_t)npix * 4));
+        if (c->disp) (void)sync_all(c);
+        c->disp = std::move(img);
         c->disp_width = c->width; c->disp_height = c->height;
     }
     const float w2 = p.white * p.white;
@@ -2476,19 +2464,16 @@ int pnrt_read_display(pnrt_ctx* c, uint8_t* out) {
     if (!c->disp) return set_err(c, PNRT_E_STATE, "read_display: display first");
     if (c->disp_width != c->width || c->disp_height != c->height)
         return set_err(c, PNRT_E_STATE, "read_display: the display image has another size than the frame: display again");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->disp, (size_t)c->width * c->height * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, sync_all(c));
-    return check_fault(c);
+    return read_back(c, out, c->disp, (size_t)c->width * c->height * 4);
 }
 
-void* pnrt_display_device_ptr(pnrt_ctx* c) { return c ? c->disp : nullptr; }
+void* pnrt_display_device_ptr(pnrt_ctx* c) { return c ? c->disp.p : nullptr; }
 
 int pnrt_luma_histogram_read(pnrt_ctx* c, int source, const void* src_device, int band, int nsh, int shard,
                              pnrt_luma_histogram* out) {
     if (!c || !out) return PNRT_E_ARG;
-    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "luma_histogram_read: bad shard selector");
     int rc;
+    if ((rc = check_selector(c, "luma_histogram_read", band, nsh, shard))) return rc;
     const float4* src = display_source(c, "luma_histogram_read", source, src_device, &rc);
     if (!src) return rc;
     if ((rc = check_fault(c))) return rc;        // completed work that faulted
@@ -2498,7 +2483,7 @@ int pnrt_luma_histogram_read(pnrt_ctx* c, int source, const void* src_device, in
     const int rows = shard_rows(c->height, band, nsh, shard);
     const size_t total = (size_t)rows * c->width;
     if (total) {
-        if (!c->luma_hist) HIPCHK(c, hipMalloc(&c->luma_hist, sizeof(LumaHist)));
+        if ((rc = c->luma_hist.reserve(c, sizeof(LumaHist)))) return rc;
         HIPCHK(c, hipMemsetAsync(c->luma_hist, 0, sizeof(LumaHist), c->stream));
         const unsigned grid = (unsigned)std::min<size_t>((total + LUMA_HIST_BLOCK - 1) / LUMA_HIST_BLOCK, LUMA_HIST_MAX_BLOCKS);
         {
@@ -2570,7 +2555,7 @@ int pnrt_profile_read(pnrt_ctx* c, pnrt_profile* out) {
 int pnrt_pack_rows(pnrt_ctx* c, void* dst, int band, int nsh, int shard) {
     if (!c || !dst) return PNRT_E_ARG;
     if (!c->accum) return set_err(c, PNRT_E_STATE, "pack_rows: no frame");
-    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "pack_rows: bad shard selector");
+    if (int rc = check_selector(c, "pack_rows", band, nsh, shard)) return rc;
     if (int rc = check_fault(c)) return rc;      // completed work that faulted
     HIPCHK(c, hipSetDevice(c->device));
     int rows = shard_rows(c->height, band, nsh, shard);
@@ -2585,7 +2570,7 @@ int pnrt_pack_rows(pnrt_ctx* c, void* dst, int band, int nsh, int shard) {
 int pnrt_unpack_rows(pnrt_ctx* c, const void* src, void* image, int band, int nsh, int shard) {
     if (!c || !src || !image) return PNRT_E_ARG;
     if (c->width <= 0 || c->height <= 0) return set_err(c, PNRT_E_STATE, "unpack_rows: no frame");
-    if (band < 1 || nsh < 1 || shard < 0 || shard >= nsh) return set_err(c, PNRT_E_ARG, "unpack_rows: bad shard selector");
+    if (int rc = check_selector(c, "unpack_rows", band, nsh, shard)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     int rows = shard_rows(c->height, band, nsh, shard);
     size_t total = (size_t)rows * c->width;
@@ -2618,11 +2603,11 @@ int pnrt_get_device_info(pnrt_ctx* c, pnrt_device_info* info) {
 int pnrt_debug_math(pnrt_ctx* c, int fn, const float* a, const float* b, float* out, int n) {
     if (!c || !a || !out || n <= 0) return PNRT_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    float *da, *db, *dout;
+    DevBuf<float> da, db, dout;
     size_t bytes = (size_t)n * 4;
-    HIPCHK(c, hipMalloc(&da, bytes));
-    HIPCHK(c, hipMalloc(&db, bytes));
-    HIPCHK(c, hipMalloc(&dout, bytes));
+    HIPCHK(c, da.alloc(bytes));
+    HIPCHK(c, db.alloc(bytes));
+    HIPCHK(c, dout.alloc(bytes));
     HIPCHK(c, hipMemcpy(da, a, bytes, hipMemcpyHostToDevice));
     if (b) HIPCHK(c, hipMemcpy(db, b, bytes, hipMemcpyHostToDevice));
     else HIPCHK(c, hipMemset(db, 0, bytes));
@@ -2630,7 +2615,6 @@ int pnrt_debug_math(pnrt_ctx* c, int fn, const float* a, const float* b, float* 
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, sync_all(c));
     HIPCHK(c, hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
     return PNRT_OK;
 }
 
@@ -2639,12 +2623,11 @@ int pnrt_debug_math(pnrt_ctx* c, int fn, const float* a, const float* b, float* 
 // ---- GPU BuildBVH (pt_bvh.h) -----------------------------------------------------------------
 namespace {
 struct DevAllocs {                     // device scratch of one build, freed on every return path
-    std::vector<void*> p;
-    ~DevAllocs() { for (void* q : p) (void)hipFree(q); }
+    std::vector<DevBuf<void>> p;
     template <typename T> hipError_t get(T** out, size_t count) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, count * sizeof(T) + 16);
-        if (e == hipSuccess) { p.push_back(q); *out = static_cast<T*>(q); }
+        p.emplace_back();
+        hipError_t e = p.back().alloc(count * sizeof(T) + 16);
+        if (e == hipSuccess) *out = static_cast<T*>(p.back().p);
         return e;
     }
 };
