@@ -426,11 +426,11 @@ static inline int fint(float f) { return (int)f; }   // GLSL int(float)
 
 // Wavefront buffers of one batch of n path slots, carved from `base` (wf_layout):
 // two path-state sets (P0-P7 + block counts), hit / occ, the env ray records,
-// segment counts, dequeue counters + census words (+ the timing builds' stamps).
+// the light and continuation entry lists (a byte per path each), segment counts, dequeue counters + census words (+ the timing builds' stamps).
 #define WF_SOBOL_BYTES (4 * WF_MAX_CHUNK_FRAMES * 8)   // the batch's Sobol table: bounces 1..3 x frames, float2
 static size_t wf_bytes(size_t n) {
     const size_t npad = (n + 255) / 256 * 256, nseg = npad / 256;
-    return 2 * (npad * 16 * 8 + nseg * 4 + 256) + n * (4 + 2) + 256 + npad * 32 + nseg * 12 + 256 + WF_SOBOL_BYTES +
+    return 2 * (npad * 16 * 8 + nseg * 4 + 256) + n * (4 + 2) + 256 + npad * 32 + npad * 2 + nseg * 12 + 256 + WF_SOBOL_BYTES +
            WF_COUNTER_BYTES + 512 +
            (WF_TIMING ? (size_t)64 * 1024 * 1024 : 0);
 }
@@ -439,6 +439,7 @@ static size_t wf_bytes(size_t n) {
 struct WfLayout {
     WfBufs b;
     PathSet set[2];
+    uint8_t *lidx, *cidx;      // [npad] each
 };
 static WfLayout wf_layout(char* base, size_t n) {
     WfLayout L;
@@ -464,6 +465,10 @@ static WfLayout wf_layout(char* base, size_t n) {
     const size_t rec = (size_t)b.npad * 16;
     b.rayO = reinterpret_cast<float4*>(base + off); off += rec;
     b.rayD = reinterpret_cast<float4*>(base + off); off += rec;
+    // entry lists of the state-traced kinds: WfLayout keeps them, a launch gets the ones it uses (render_batch)
+    L.lidx = reinterpret_cast<uint8_t*>(base + off); off += b.npad;
+    L.cidx = reinterpret_cast<uint8_t*>(base + off); off += b.npad;
+    b.lidx = b.cidx = nullptr;
     b.segcount = reinterpret_cast<unsigned int*>(base + off); off += (size_t)b.nseg_k * 12;
     off = (off + 255) & ~(size_t)255;
     b.sobol = reinterpret_cast<float2*>(base + off); off += WF_SOBOL_BYTES;
@@ -542,6 +547,9 @@ static int report_trace_diag(pnrt_ctx* c, const WfBufs& b, hipStream_t st, int b
         HIPCHK(c, hipMemcpy(stt, b.stats, sizeof stt, hipMemcpyDeviceToHost));
         // shadow rays the bounce's setup found moot (pt_wf.h WF_SKIP_MOOT: not traced)
         fprintf(stderr, "[trace moot] bounce %d light=%llu env=%llu cont=%llu\n", bounce, stt[56], stt[57], stt[58]);
+        // the live path entries the setup left, and the rays the trace loaded, by kind
+        fprintf(stderr, "[trace loaded] bounce %d entries=%llu light=%llu env=%llu cont=%llu\n", bounce, stt[62], stt[59],
+                stt[60], stt[61]);
         HIPCHK(c, hipMemsetAsync(b.stats + 56, 0, 64, st));
         for (int k = 0; k < 3; ++k) {        // lane steps per ray, log2 buckets, by ray kind
             fprintf(stderr, "[trace hist] bounce %d kind %d:", bounce, k);
@@ -608,6 +616,11 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
             b.rd = L.set[bounce & 1];
             b.wr = L.set[(bounce + 1) & 1];
             const bool fin = bounce + 1 == fp.max_depth;   // every path ends: no setup half, no rays
+            // this setup's moot test drops light rays, and continuation rays where it sets up
+            // the last bounce: those kinds go through their entry lists, in the setup and in
+            // the trace launch that follows it (gen has no test: whole ranges, no lists)
+            b.lidx = L.lidx;
+            b.cidx = bounce + 2 == fp.max_depth ? L.cidx : nullptr;
             if (ad && fin)
                 hipLaunchKernelGGL((pt_wf_shade_setup<true, WfAdapt>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
             else if (ad)

@@ -54,7 +54,9 @@
 // Ray kinds: 0 light shadow, 1 env shadow, 2 continuation.  Only env shadow rays
 // are queued as ready-to-trace records (rayO / rayD): continuation and light
 // shadow rays are traced from the path state the setup wrote (P0 with P1 / P7,
-// see wf_enqueue; queued records for them measured 2 % / 3.3 % slower).
+// see wf_enqueue; queued records for them measured 2 % / 3.3 % slower) -- the
+// block's whole live range, or, where the setup's moot test dropped some, the
+// entries a one-byte list names (WfBufs::lidx / cidx).
 #define WF_QUEUED(k) ((k) == 1)
 
 // Cache policy of the streamed path-state traffic (path state, ray records,
@@ -121,6 +123,13 @@ struct WfBufs {
     float4* rayO;            // [npad]  (.w = path entry j)
     float4* rayD;            // [npad]
     unsigned int* segcount;  // [3 * nseg_k]
+    // entry lists of the two kinds traced from the path state, set per launch by
+    // the host where the setup's moot test can leave a live entry without that ray
+    // (light: every shade setup; continuation: the last bounce's); null where
+    // every live entry has the ray and the segment is the block's live range.
+    // Slot 256 j + r holds the entry, less 256 j, of segment j's r-th ray.
+    uint8_t* lidx;           // [npad] light shadow rays
+    uint8_t* cidx;           // [npad] continuation rays
     uint32_t npad;           // n rounded up to 256
     uint32_t nseg_k;         // setup blocks = segments per kind
     unsigned long long* stats; // WF_STATS builds: traversal step census (8 counters)
@@ -534,9 +543,9 @@ PN_DEV uint32_t wf_setup_core(const DevScene& s, const FrameParams& fp, const Wf
         // at +0 and only takes round-to-nearest sums, so Lo + (+-0) = Lo) -- the term
         // lies below Lo's rounding, or cw / LD / LE is zero.  Both rays are then
         // moot: their meta bits are cleared (the shade adds the "occluded" term,
-        // which leaves Lo), the env ray is not queued, and the light ray (traced from
-        // the path state) gets a NaN direction, which the trace's root box test
-        // rejects.  A NaN or infinite operand, or a zero denominator, makes T NaN or
+        // which leaves Lo) and neither is queued: the env ray gets no record, the
+        // light ray (traced from the path state) no slot in the block's entry list
+        // (wf_enqueue), so the trace never loads it.  A NaN or infinite operand, or a zero denominator, makes T NaN or
         // infinite: no skip; nor is there one where a reciprocal falls below 2^-126
         // (where v_rcp_f32 may return 0, no bound).
         //
@@ -548,8 +557,10 @@ PN_DEV uint32_t wf_setup_core(const DevScene& s, const FrameParams& fp, const Wf
         // rcp(|dPDF|) (1 + 2^-20) bounds it the same way.  The ray is moot where Tc
         // is 0 (the term is +-0 for every outcome: Lo1 + +-0 = Lo1, Lo1 never -0) or
         // where Lo1 = Lo is proven (the test above) and Lo + Tc, Lo - Tc round to Lo.
-        // Then P1 gets a NaN direction (the trace misses it) and NdotL = -1 (never
-        // a real value, |N.L| >= 0), which the shade reads as "write Lo1".
+        // Then the ray gets no slot in the continuation entry list and no trace result;
+        // P1 gets NdotL = -1 (never a real value, |N.L| >= 0), which the shade reads as
+        // "a miss, write Lo1" whatever hit[] holds, and a NaN direction (a launch
+        // without the list traces the whole range: its root box test rejects the ray).
         const bool last = bounce + 1 == fp.max_depth;
         if ((nfl & (WF_RLIGHT | WF_RENV)) || last) {
             // the candidates read back from the lane's own LDS slot (or from what P3 / P4
@@ -595,9 +606,6 @@ PN_DEV uint32_t wf_setup_core(const DevScene& s, const FrameParams& fp, const Wf
                     if (nfl & WF_RLIGHT) atomicAdd(&b.stats[56], 1ull);
                     if (nfl & WF_RENV) atomicAdd(&b.stats[57], 1ull);
                 }
-                if (nfl & WF_RLIGHT)
-                    ps_st(w.P7, i, make_float4(__uint_as_float(0x7fc00000u), __uint_as_float(0x7fc00000u),
-                                               __uint_as_float(0x7fc00000u), 0.f));
                 nfl &= ~(WF_RLIGHT | WF_RENV);
             }
         }
@@ -607,7 +615,7 @@ PN_DEV uint32_t wf_setup_core(const DevScene& s, const FrameParams& fp, const Wf
     const uint32_t meta = slot | ((nfl & WF_RLIGHT) ? WF_META_RL : 0u) | ((nfl & WF_RENV) ? WF_META_RE : 0u) |
                           ((uint32_t)bounce << WF_META_BSHIFT);
     ps_st(w.P6, i, make_float4(q.cw.x, q.cw.y, q.cw.z, __uint_as_float(meta)));
-    return nfl | WF_RCONT;
+    return contMoot ? nfl : nfl | WF_RCONT;
 }
 
 // Compact the block's rays of each kind into its own queue segment: a ballot
@@ -621,11 +629,20 @@ PN_DEV uint32_t wf_setup_core(const DevScene& s, const FrameParams& fp, const Wf
 // entries [256 j, 256 j + total) -- so the segment of such a kind IS that range
 // of the path state: origin P0.xyz (the offset origin both kinds start from),
 // direction P1.xyz (continuation) or P7.xyz (light), the same floats a ray
-// record would copy.  Only the count is stored.  The env shadow rays (drawn only
+// record would copy.  Only the count is stored.  That holds for gen's rays and for
+// the continuation rays of every bounce but the last; a setup with the moot test
+// (wf_setup_core) drops light rays, and at the last bounce continuation rays, so
+// there the kind's segment is a list of one-byte entries (b.lidx / b.cidx, set by
+// the host for exactly those launches) holding only the entries that have the ray:
+// the trace never loads, starts or steps a dead one, and its lane goes to a real
+// ray instead of idling until the wave's next refill.  The env shadow rays (drawn only
 // where the sampled direction is above the surface) are queued as records.  The
 // wave that passes through here last writes the block's counts (its acquire sees
 // every other wave's counter updates).  (Grouping a segment's rays by direction
 // octant measured neutral for both queued and state-traced kinds.)
+// LISTS: the setup runs the moot test, so the state-traced kinds may go through their
+// entry lists (gen: no test, no list code).
+template <bool LISTS>
 PN_DEV void wf_enqueue(const WfBufs& b, uint32_t i, uint32_t nfl, const BounceRays& rays, bool lights) {
     uint32_t* ec = wf_enq_ctr();
     const int lane = threadIdx.x & 63;
@@ -641,15 +658,33 @@ PN_DEV void wf_enqueue(const WfBufs& b, uint32_t i, uint32_t nfl, const BounceRa
             ps_st(b.rayD, slot, make_float4(rays.dE.x, rays.dE.y, rays.dE.z, 0.f));
         }
     }
+    // a state-traced kind whose entry list is in use (wave-uniform): one byte per ray,
+    // the entry within the block, at the kind's next slots of the block's 256
+    auto list = [&](uint8_t* idx, uint32_t kind, bool has) {
+        if (!LISTS || !idx) return;
+        const uint64_t m = __ballot(has);
+        uint32_t base = 0;
+        if (lane == 0 && m != 0)
+            base = __hip_atomic_fetch_add(ec + kind, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (has) {
+            const size_t slot = PT_CHECK(b.fault, (size_t)blockIdx.x * 256 + base + lanes_below(m), b.npad, PT_SITE_RAY);
+            idx[slot] = (uint8_t)(i - blockIdx.x * 256u);
+        }
+    };
+    list(b.lidx, 0u, (nfl & WF_RLIGHT) != 0u);
+    list(b.cidx, 2u, (nfl & WF_RCONT) != 0u);
     uint32_t done = 0;
     if (lane == 0) done = __hip_atomic_fetch_add(ec + 3, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (__builtin_amdgcn_readfirstlane(done) == blockDim.x / 64 - 1) {
         const uint32_t tot = __hip_atomic_load(wf_live_ctr(), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (lane < 3) {
             const uint32_t qn = __hip_atomic_load(ec + lane, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            b.segcount[lane * b.nseg_k + blockIdx.x] = WF_QUEUED(lane) ? qn : ((lane == 2 || lights) ? tot : 0u);
+            const bool counted = WF_QUEUED(lane) || (LISTS && (lane == 0 ? b.lidx != nullptr : b.cidx != nullptr));
+            b.segcount[lane * b.nseg_k + blockIdx.x] = counted ? qn : ((lane == 2 || lights) ? tot : 0u);
         }
         if (lane == 0) b.wr.bcount[blockIdx.x] = tot;
+        if (WF_STATS && lane == 0) atomicAdd(&b.stats[62], (unsigned long long)tot);     // census: live entries
     }
 }
 
@@ -719,7 +754,7 @@ __global__ void __launch_bounds__(256, WF_GEN_WAVES) pt_wf_gen_setup(DevScene s,
     uint32_t nfl = 0;
     BounceRays rays;
     if (cont) nfl = wf_setup_core<true, false, false>(s, fp, b, j, i, 0, x, py, frame, q, rays);
-    wf_enqueue(b, j, nfl, rays, s.n_lights > 0);     // every lane of the wave reaches this point
+    wf_enqueue<false>(b, j, nfl, rays, s.n_lights > 0);     // every lane of the wave reaches this point
 }
 
 // ---- trace: every ray of the bounce, persistent waves, LDS short stack ------------------------
@@ -1386,8 +1421,12 @@ PN_DEV void wf_load_ray(const WfBufs& b, uint32_t kind, uint32_t slot, int mode,
     // slot = kind * npad + position e in the kind's range; kinds traced from the
     // state the setup wrote read path entry e, the queued kind its record (see
     // wf_enqueue)
-    const uint32_t e = (uint32_t)PT_CHECK(b.fault, slot - kind * b.npad, b.npad, PT_SITE_RAY);
+    uint32_t e = (uint32_t)PT_CHECK(b.fault, slot - kind * b.npad, b.npad, PT_SITE_RAY);
     const bool fromState = !WF_QUEUED(kind);     // wave-uniform
+    // ... through the kind's entry list where the launch has one (wave-uniform): the
+    // position names a byte, the entry within the position's 256-entry block
+    const uint8_t* idx = kind == 0 ? b.lidx : kind == 2 ? b.cidx : nullptr;
+    if (idx) e = (uint32_t)PT_CHECK(b.fault, (e & ~255u) + __builtin_nontemporal_load(idx + e), b.npad, PT_SITE_RAY);
     const float4* O = fromState ? b.wr.P0 : b.rayO;
     const float4* D = fromState ? (kind == 0 ? b.wr.P7 : b.wr.P1) : b.rayD;
     const float4 ro = ps_ld(O + e), rd = ps_ld(D + e);
@@ -1483,6 +1522,7 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, CC ? WF_TRACE_WAVES_CC : WF_TR
     uint64_t last_ray = 0;      // WF_TIMING builds: (iteration, kind, lane steps) of the lane's last finished ray
     uint32_t witer = 0, witer_exh = 0;
     unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // iters, active, tri, node, idle-pop, refill, rays, -
+    unsigned long long ldk[3] = {0, 0, 0};                 // rays the wave loaded, by kind
 
     // dequeue the wave's next queue item into [next, end) / ckind, or set `exhausted`
     // (wave-uniform; lane 0 issues the atomic)
@@ -1637,6 +1677,7 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, CC ? WF_TRACE_WAVES_CC : WF_TR
             if (idle != 0 && next >= end && !exhausted) bclaim((uint32_t)__popcll(idle));
             if (idle != 0 && next < end) {
                 const uint32_t myid = next + lanes_below(idle);
+                if (WF_STATS) ldk[ckind] += min((uint32_t)__popcll(idle), end - next);     // census: rays loaded, by kind
                 next = min(next + (uint32_t)__popcll(idle), end);
                 if (busy == 0 && myid < end) {
                     const uint32_t kind = ckind;
@@ -1813,8 +1854,10 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, CC ? WF_TRACE_WAVES_CC : WF_TR
         __syncthreads();
         if (threadIdx.x < 48 && hist[threadIdx.x]) atomicAdd(b.stats + 8 + threadIdx.x, (unsigned long long)hist[threadIdx.x]);
     }
-    if (WF_STATS && lane == 0)
+    if (WF_STATS && lane == 0) {
         for (int k = 0; k < 8; ++k) atomicAdd(b.stats + k, st[k]);
+        for (int k = 0; k < 3; ++k) atomicAdd(b.stats + 59 + k, ldk[k]);
+    }
 }
 
 // ---- primary hits through the trace kernel's step --------------------------------------------
@@ -1900,13 +1943,16 @@ PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs
     i = (uint32_t)PT_CHECK(b.fault, i, b.npad, PT_SITE_PATH);
     const float4 p0 = ps_ld(rd.P0 + i), p1 = ps_ld(rd.P1 + i), p6 = ps_ld(rd.P6 + i);
     const float4 p2 = ps_ld(rd.P2 + i), p5 = ps_ld(rd.P5 + i);
-    const int ht = b.hit[i];
+    const int ht_traced = b.hit[i];
     // the light / env candidates are read only where they count: an occluded
     // light ray zeroes LDirect and lightPDF (:890), an occluded or absent env ray
     // zeroes LEnvironment (:922; enPDF is kept, in P2.w).  Lanes that need neither
     // read the scene's zero float4 instead (no branch: both loads issue together).
     const uint32_t oc = reinterpret_cast<const uint16_t*>(b.occ)[i];      // both bytes in one load
     asm volatile("" ::: "memory");     // keep the hit load in this first batch (the scheduler sinks it)
+    // a moot continuation ray (NdotL = -1, wf_setup_core) was not traced: its hit[] word
+    // is an earlier launch's -- the ray is a miss
+    const int ht = p1.w == -1.f ? -1 : ht_traced;
     const uint32_t meta = __float_as_uint(p6.w);
     bounce = (int)(meta >> WF_META_BSHIFT);
     slot = meta & WF_META_SLOT;
@@ -1990,5 +2036,5 @@ __global__ void __launch_bounds__(256, FINAL ? 8 : WF_SHADE_WAVES) pt_wf_shade_s
     uint32_t nfl = 0;
     BounceRays rays;
     if (cont) nfl = wf_setup_core<false, true, true>(s, fp, b, j, slot, bounce, x, py, frame, q, rays);
-    wf_enqueue(b, j, nfl, rays, s.n_lights > 0);     // every lane of the wave reaches this point
+    wf_enqueue<true>(b, j, nfl, rays, s.n_lights > 0);     // every lane of the wave reaches this point
 }
