@@ -24,6 +24,7 @@ INC = os.path.join(REPO, "include")
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("PNRT_OFFLOAD_ARCH", "gfx950")
+ROCM = "/opt/rocm"             # headers and libraries of the HIP runtime and RCCL, for the callers that use them
 
 DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
@@ -62,17 +63,27 @@ def device_source_hash() -> str:
     return h.hexdigest()[:16]
 
 
+# Every device compile -- the product, the diagnostic variants, the tools' listings and the
+# tests' switch builds -- takes these flags, so that all of them vouch for the product's code.
+# No SLP packing into v_pk_*_f32: the register pairs it needs cost the trace kernel a wave
+# per SIMD and the setup kernels one.
+DEVICE_FLAGS = ["-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-fno-gpu-rdc", "-fno-slp-vectorize"]
+
+
+def _device_deps():
+    return [os.path.join(CSRC, d) for d in DEVICE_DEPS] + [os.path.join(INC, "pnrt.h")]
+
+
+def device_cmd(out, extra=(), opt="-O3", src_hash=None):
+    """The command line that compiles the device sources into `out`."""
+    return [HIPCC, f"--offload-arch={ARCH}", opt, *DEVICE_FLAGS, f'-DPNRT_SRC_HASH="{src_hash or device_source_hash()}"',
+            "-I", INC, *extra, *[os.path.join(CSRC, s) for s in DEVICE_SRCS], "-o", out]
+
+
 def build_device(force=False, extra=()):
     out = os.path.join(PKG, "libpnrt.so")
-    deps = [os.path.join(CSRC, d) for d in DEVICE_DEPS] + [os.path.join(INC, "pnrt.h")]
-    if force or extra or _stale(out, deps):
-        cmd = [HIPCC, f"--offload-arch={ARCH}", os.environ.get("PNRT_OPT", "-O3"), "-std=c++17", "-fPIC", "-shared",
-               "-ffp-contract=off", "-fno-fast-math", "-fno-gpu-rdc",
-               # no SLP packing into v_pk_*_f32: the register pairs it needs cost the
-               # trace kernel a wave per SIMD and the setup kernels one
-               "-fno-slp-vectorize", f'-DPNRT_SRC_HASH="{device_source_hash()}"', "-I", INC,
-               *extra, *[os.path.join(CSRC, s) for s in DEVICE_SRCS], "-o", out]
-        _run(cmd)
+    if force or extra or _stale(out, _device_deps()):
+        _run(device_cmd(out, extra, os.environ.get("PNRT_OPT", "-O3")))
     return out
 
 
@@ -99,108 +110,74 @@ def variant_path(name: str) -> str:
 
 
 def build_diag_variants(force=False):
-    deps = [os.path.join(CSRC, d) for d in DEVICE_DEPS] + [os.path.join(INC, "pnrt.h")]
     os.makedirs(os.path.join(PKG, "variants"), exist_ok=True)
     for name, flags in DIAG_VARIANTS.items():
         out = variant_path(name)
-        if force or _stale(out, deps):
-            _run([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                  "-fno-fast-math", "-fno-gpu-rdc", "-fno-slp-vectorize", f'-DPNRT_SRC_HASH="{device_source_hash()}"',
-                  "-I", INC, *flags, *[os.path.join(CSRC, s) for s in DEVICE_SRCS], "-o", out])
+        if force or _stale(out, _device_deps()):
+            _run(device_cmd(out, flags))
+
+
+# TEST-ONLY compiled callers of include/pnrt.h (and include/pnrt_host.h), which exercise the
+# drop-in boundary without Python: tests/abi/<source> -> tests/abi/<name>, .cpp with g++, .c as
+# C11 with gcc.  Each is linked against libpnrt.so and the libraries listed here; one that lists
+# -lpnrt_host depends on the host library and its header too.
+ABI_CALLERS = {
+    "c_abi_render.cpp": ["-lpnrt_host"],     # a render through both libraries (tests/test_gpu_c_abi.py)
+    "c_abi_dloop.cpp": [],                   # the reference's render loop (one pnrt_render per frame), for parity and timing
+    "c_abi_denoise.c": [],                   # the guide images and the denoised preview (tests/test_gpu_denoise_c_abi.py)
+    "c_abi_convergence.c": [],               # the sample moments and the convergence statistics (tests/test_gpu_moments_c_abi.py)
+    "c_abi_query.c": [],                     # ray queries, both kinds (tests/test_gpu_query_c_abi.py)
+    "c_abi_denoise_variance.c": [],          # the variance-guided preview (tests/test_gpu_denoise_variance_c_abi.py)
+    "c_abi_reproject.c": [],                 # temporal reprojection (tests/test_gpu_reproject_c_abi.py)
+    "c_abi_display.c": [],                   # the display transform and auto exposure (tests/test_gpu_display_c_abi.py)
+    # the multi-GPU caller: one process, one RCCL communicator per device (ncclCommInitAll + ncclGather)
+    "c_abi_multigpu.cpp": ["-lpnrt_host", "-lamdhip64", "-lrccl"],
+    # an in-place geometry edit: pnrt_update_vertices, pnrt_read_bvh_boxes (tests/test_gpu_refit_c_abi.py)
+    "c_abi_refit.c": [],
+    # a camera sequence (pnrt_camera_sequence) rendered with pnrt_render_cameras (tests/test_gpu_cameras.py)
+    "c_abi_cameras.c": ["-lpnrt_host", "-lm"],
+}
+
+
+def _abi_caller(source, force):
+    """Compile one caller where it is stale; None when its source, a header or a library is missing."""
+    libs = ABI_CALLERS[source]
+    src = os.path.join(REPO, "tests", "abi", source)
+    out = os.path.splitext(src)[0]
+    deps = [src, os.path.join(INC, "pnrt.h"), os.path.join(PKG, "libpnrt.so")]
+    if "-lpnrt_host" in libs:
+        deps += [os.path.join(INC, "pnrt_host.h"), os.path.join(PKG, "libpnrt_host.so")]
+    if not all(os.path.exists(d) for d in deps):
+        return None
+    if force or _stale(out, deps):
+        cc = ["g++", "-std=c++17"] if source.endswith(".cpp") else ["gcc", "-std=c11"]
+        hip = "-lamdhip64" in libs           # the caller uses the HIP runtime itself: ROCm's headers and libraries
+
+        def rocm(*args):
+            return list(args) if hip else []
+        _run([*cc, "-O2", "-Wall", *rocm("-D__HIP_PLATFORM_AMD__"), "-I", INC, *rocm("-I", f"{ROCM}/include"), src, "-o", out,
+              "-L", PKG, *rocm("-L", f"{ROCM}/lib"), "-lpnrt", *libs, "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd",
+              *rocm(f"-Wl,-rpath,{ROCM}/lib"), f"-Wl,-rpath-link,{ROCM}/lib"])
+    return out
 
 
 def build_abi_caller(force=False):
-    """tests/abi/c_abi_render: a compiled C++ caller of include/pnrt.h +
-    include/pnrt_host.h linked against the two libraries (TEST-ONLY; exercises
-    the drop-in boundary without Python, tests/test_gpu_c_abi.py)."""
-    src = os.path.join(REPO, "tests", "abi", "c_abi_render.cpp")
-    out = os.path.join(REPO, "tests", "abi", "c_abi_render")
-    deps = [src, os.path.join(INC, "pnrt.h"), os.path.join(INC, "pnrt_host.h"),
+    """tests/abi/c_abi_render and the callers that came with it (every ABI_CALLERS entry but the two below);
+    None, and nothing built, without c_abi_render's source, both headers and both libraries."""
+    need = [os.path.join(REPO, "tests", "abi", "c_abi_render.cpp"), os.path.join(INC, "pnrt.h"), os.path.join(INC, "pnrt_host.h"),
             os.path.join(PKG, "libpnrt.so"), os.path.join(PKG, "libpnrt_host.so")]
-    if not os.path.exists(src) or not all(os.path.exists(d) for d in deps):
+    if not all(os.path.exists(d) for d in need):
         return None
-    if force or _stale(out, deps):
-        _run(["g++", "-std=c++17", "-O2", "-Wall", "-I", INC, src, "-o", out, "-L", PKG, "-lpnrt", "-lpnrt_host",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
-    # the reference's render loop (one pnrt_render per frame) through the C ABI alone, for parity and timing
-    dsrc = os.path.join(REPO, "tests", "abi", "c_abi_dloop.cpp")
-    dout = os.path.join(REPO, "tests", "abi", "c_abi_dloop")
-    if os.path.exists(dsrc) and (force or _stale(dout, deps[1:2] + deps[3:4] + [dsrc])):
-        _run(["g++", "-std=c++17", "-O2", "-Wall", "-I", INC, dsrc, "-o", dout, "-L", PKG, "-lpnrt",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
-    # the guide images and the denoised preview from a C translation unit (tests/test_gpu_denoise_c_abi.py)
-    csrc = os.path.join(REPO, "tests", "abi", "c_abi_denoise.c")
-    cout = os.path.join(REPO, "tests", "abi", "c_abi_denoise")
-    if os.path.exists(csrc) and (force or _stale(cout, deps[1:2] + deps[3:4] + [csrc])):
-        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, csrc, "-o", cout, "-L", PKG, "-lpnrt",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
-    # the sample moments and the convergence statistics from a C translation unit (tests/test_gpu_moments_c_abi.py)
-    vsrc = os.path.join(REPO, "tests", "abi", "c_abi_convergence.c")
-    vout = os.path.join(REPO, "tests", "abi", "c_abi_convergence")
-    if os.path.exists(vsrc) and (force or _stale(vout, deps[1:2] + deps[3:4] + [vsrc])):
-        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, vsrc, "-o", vout, "-L", PKG, "-lpnrt",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
-    # ray queries, both kinds, from a C translation unit (tests/test_gpu_query_c_abi.py)
-    qsrc = os.path.join(REPO, "tests", "abi", "c_abi_query.c")
-    qout = os.path.join(REPO, "tests", "abi", "c_abi_query")
-    if os.path.exists(qsrc) and (force or _stale(qout, deps[1:2] + deps[3:4] + [qsrc])):
-        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, qsrc, "-o", qout, "-L", PKG, "-lpnrt",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
-    # the variance-guided preview from a C translation unit (tests/test_gpu_denoise_variance_c_abi.py)
-    dvsrc = os.path.join(REPO, "tests", "abi", "c_abi_denoise_variance.c")
-    dvout = os.path.join(REPO, "tests", "abi", "c_abi_denoise_variance")
-    if os.path.exists(dvsrc) and (force or _stale(dvout, deps[1:2] + deps[3:4] + [dvsrc])):
-        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, dvsrc, "-o", dvout, "-L", PKG, "-lpnrt",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
-    # temporal reprojection from a C translation unit (tests/test_gpu_reproject_c_abi.py)
-    rsrc = os.path.join(REPO, "tests", "abi", "c_abi_reproject.c")
-    rout = os.path.join(REPO, "tests", "abi", "c_abi_reproject")
-    if os.path.exists(rsrc) and (force or _stale(rout, deps[1:2] + deps[3:4] + [rsrc])):
-        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, rsrc, "-o", rout, "-L", PKG, "-lpnrt",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
-    # the display transform and auto exposure from a C translation unit (tests/test_gpu_display_c_abi.py)
-    psrc = os.path.join(REPO, "tests", "abi", "c_abi_display.c")
-    pout = os.path.join(REPO, "tests", "abi", "c_abi_display")
-    if os.path.exists(psrc) and (force or _stale(pout, deps[1:2] + deps[3:4] + [psrc])):
-        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, psrc, "-o", pout, "-L", PKG, "-lpnrt",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
-    # the multi-GPU caller: one process, one RCCL communicator per device (ncclCommInitAll + ncclGather)
-    msrc = os.path.join(REPO, "tests", "abi", "c_abi_multigpu.cpp")
-    mout = os.path.join(REPO, "tests", "abi", "c_abi_multigpu")
-    if os.path.exists(msrc) and (force or _stale(mout, deps[1:] + [msrc])):
-        _run(["g++", "-std=c++17", "-O2", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", INC, "-I", "/opt/rocm/include", msrc,
-              "-o", mout, "-L", PKG, "-L", "/opt/rocm/lib", "-lpnrt", "-lpnrt_host", "-lamdhip64", "-lrccl",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
-    return out
+    outs = [_abi_caller(source, force) for source in ABI_CALLERS if source not in ("c_abi_refit.c", "c_abi_cameras.c")]
+    return outs[0]
 
 
 def build_refit_abi_caller(force=False):
-    """tests/abi/c_abi_refit: an in-place geometry edit (pnrt_update_vertices,
-    pnrt_read_bvh_boxes) from a C translation unit (TEST-ONLY; tests/test_gpu_refit_c_abi.py)."""
-    src = os.path.join(REPO, "tests", "abi", "c_abi_refit.c")
-    out = os.path.join(REPO, "tests", "abi", "c_abi_refit")
-    deps = [src, os.path.join(INC, "pnrt.h"), os.path.join(PKG, "libpnrt.so")]
-    if not all(os.path.exists(d) for d in deps):
-        return None
-    if force or _stale(out, deps):
-        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, src, "-o", out, "-L", PKG, "-lpnrt",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
-    return out
+    return _abi_caller("c_abi_refit.c", force)
 
 
 def build_cameras_abi_caller(force=False):
-    """tests/abi/c_abi_cameras: a camera sequence (pnrt_camera_sequence) rendered with
-    pnrt_render_cameras from a C translation unit (TEST-ONLY; tests/test_gpu_cameras.py)."""
-    src = os.path.join(REPO, "tests", "abi", "c_abi_cameras.c")
-    out = os.path.join(REPO, "tests", "abi", "c_abi_cameras")
-    deps = [src, os.path.join(INC, "pnrt.h"), os.path.join(INC, "pnrt_host.h"), os.path.join(PKG, "libpnrt.so"),
-            os.path.join(PKG, "libpnrt_host.so")]
-    if not all(os.path.exists(d) for d in deps):
-        return None
-    if force or _stale(out, deps):
-        _run(["gcc", "-std=c11", "-O2", "-Wall", "-I", INC, src, "-o", out, "-L", PKG, "-lpnrt", "-lpnrt_host", "-lm",
-              "-Wl,-rpath,$ORIGIN/../../pnraytracing_amd", "-Wl,-rpath-link,/opt/rocm/lib"])
-    return out
+    return _abi_caller("c_abi_cameras.c", force)
 
 
 def build_oracle(force=False):

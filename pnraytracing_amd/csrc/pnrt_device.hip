@@ -1139,69 +1139,47 @@ static int denoise_reserve(pnrt_ctx* c, dim3* grid) {
     return PNRT_OK;
 }
 
-static int denoise(pnrt_ctx* c, const pnrt_denoise_params& p) {
+// Both denoisers (pt_denoise.h; VAR: pnrt_denoise_variance): the prep launch, then one launch per
+// level.  sigma_c: sigma_color, halved per level (VAR: sigma_variance, the same at every level).
+template <bool VAR>
+static int denoise_run(pnrt_ctx* c, int levels, float sigma_c, float sigma_n, float sigma_p) {
     dim3 grid;
     if (int rc = denoise_reserve(c, &grid)) return rc;
     DenoiseParams d{};
     d.width = c->width; d.height = c->height;
+    if (VAR) d.colour = sigma_c;             // (the fixed filter's is set per level, below; the prep reads neither)
+    d.inv_n = 1.0f / (sigma_n * sigma_n);
+    d.inv_p = 1.0f / (sigma_p * sigma_p);
     // level i reads image (first + i) & 1 and writes the other, so the last one writes dn_img[0]
-    const int first = p.levels & 1;
-    hipLaunchKernelGGL(pt_denoise_prep, grid, dim3(256), 0, c->stream, d, c->scene.materials, c->scene.n_materials,
+    const int first = levels & 1;
+    // (VAR: the moments are written by the blend launches, which this stream has queued before)
+    hipLaunchKernelGGL(pt_denoise_prep<VAR>, grid, dim3(256), 0, c->stream, d, c->scene.materials, c->scene.n_materials,
                        (const float4*)c->accum, (const float4*)c->aov[PNRT_AOV_POSITION], (const float4*)c->aov[PNRT_AOV_NORMAL],
-                       (const float4*)c->aov[PNRT_AOV_ALBEDO], c->dn_guide, c->dn_img[first]);
+                       (const float4*)c->aov[PNRT_AOV_ALBEDO], VAR ? (const float4*)c->moments : nullptr, c->dn_guide,
+                       c->dn_img[first]);
     HIPCHK(c, hipGetLastError());
-    d.inv_n = 1.0f / (p.sigma_normal * p.sigma_normal);
-    d.inv_p = 1.0f / (p.sigma_position * p.sigma_position);
-    for (int i = 0; i < p.levels; ++i) {
-        const float sc = p.sigma_color * std::ldexp(1.0f, -i);
-        d.inv_c = 1.0f / (sc * sc);
+    for (int i = 0; i < levels; ++i) {
+        if (!VAR) {
+            const float sc = sigma_c * std::ldexp(1.0f, -i);
+            d.colour = 1.0f / (sc * sc);
+        }
         d.step = 1 << i;
         const float4* src = c->dn_img[(first + i) & 1];
         float4* dst = c->dn_img[(first + i + 1) & 1];
+        const bool last = i + 1 == levels;
         // spacings 1, 2, 4 through an LDS tile with halo, 8 and 16 through the caches (pt_denoise.h)
-        const bool last = i + 1 == p.levels;
-        auto launch = [&](auto kernel) {
+        auto launch = [&](auto lds_step) {
+            constexpr int STEP = decltype(lds_step)::value;
+            const auto kernel = last ? pt_denoise_pass<VAR, STEP, true> : pt_denoise_pass<VAR, STEP, false>;
             hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, d, (const float4*)c->dn_guide, src, dst,
                                (const float4*)c->accum, (const float4*)c->aov[PNRT_AOV_ALBEDO]);
         };
-        if (d.step == 1 && DN_LDS_MAX_STEP >= 1) last ? launch(pt_denoise_pass_lds<1, true>) : launch(pt_denoise_pass_lds<1, false>);
-        else if (d.step == 2 && DN_LDS_MAX_STEP >= 2) last ? launch(pt_denoise_pass_lds<2, true>) : launch(pt_denoise_pass_lds<2, false>);
-        else if (d.step == 4 && DN_LDS_MAX_STEP >= 4) last ? launch(pt_denoise_pass_lds<4, true>) : launch(pt_denoise_pass_lds<4, false>);
-        else last ? launch(pt_denoise_pass<true>) : launch(pt_denoise_pass<false>);
-        HIPCHK(c, hipGetLastError());
-    }
-    c->dn_width = c->width; c->dn_height = c->height;
-    return mark_stream(c);
-}
-
-// pnrt_denoise_variance: the same images and ping-pong as denoise(), the kernels of pt_denoise_var.h
-static int denoise_variance(pnrt_ctx* c, const pnrt_denoise_variance_params& p) {
-    dim3 grid;
-    if (int rc = denoise_reserve(c, &grid)) return rc;
-    DenoiseVarParams d{};
-    d.width = c->width; d.height = c->height;
-    d.sigma_v = p.sigma_variance;
-    d.inv_n = 1.0f / (p.sigma_normal * p.sigma_normal);
-    d.inv_p = 1.0f / (p.sigma_position * p.sigma_position);
-    const int first = p.levels & 1;      // the last pass writes dn_img[0]
-    // the moments are written by the blend launches, which this stream has queued before
-    hipLaunchKernelGGL(pt_denoise_var_prep, grid, dim3(256), 0, c->stream, d, c->scene.materials, c->scene.n_materials,
-                       (const float4*)c->accum, (const float4*)c->aov[PNRT_AOV_POSITION], (const float4*)c->aov[PNRT_AOV_NORMAL],
-                       (const float4*)c->aov[PNRT_AOV_ALBEDO], (const float4*)c->moments, c->dn_guide, c->dn_img[first]);
-    HIPCHK(c, hipGetLastError());
-    for (int i = 0; i < p.levels; ++i) {
-        d.step = 1 << i;
-        const float4* src = c->dn_img[(first + i) & 1];
-        float4* dst = c->dn_img[(first + i + 1) & 1];
-        const bool last = i + 1 == p.levels;
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, d, (const float4*)c->dn_guide, src, dst,
-                               (const float4*)c->accum, (const float4*)c->aov[PNRT_AOV_ALBEDO]);
-        };
-        if (d.step == 1) last ? launch(pt_denoise_var_pass_lds<1, true>) : launch(pt_denoise_var_pass_lds<1, false>);
-        else if (d.step == 2) last ? launch(pt_denoise_var_pass_lds<2, true>) : launch(pt_denoise_var_pass_lds<2, false>);
-        else if (d.step == 4) last ? launch(pt_denoise_var_pass_lds<4, true>) : launch(pt_denoise_var_pass_lds<4, false>);
-        else last ? launch(pt_denoise_var_pass<true>) : launch(pt_denoise_var_pass<false>);
+        switch (d.step <= DN_LDS_MAX_STEP ? d.step : 0) {
+            case 1: launch(std::integral_constant<int, 1>{}); break;
+            case 2: launch(std::integral_constant<int, 2>{}); break;
+            case 4: launch(std::integral_constant<int, 4>{}); break;
+            default: launch(std::integral_constant<int, 0>{});
+        }
         HIPCHK(c, hipGetLastError());
     }
     c->dn_width = c->width; c->dn_height = c->height;
@@ -2144,7 +2122,7 @@ int pnrt_denoise(pnrt_ctx* c, const pnrt_denoise_params* params) {
                                         "environment or traversal mode changed): render_guides again");
     if (int rc = check_fault(c)) return rc;      // completed work that faulted
     HIPCHK(c, hipSetDevice(c->device));
-    return denoise(c, p);
+    return denoise_run<false>(c, p.levels, p.sigma_color, p.sigma_normal, p.sigma_position);
 }
 
 int pnrt_denoise_variance(pnrt_ctx* c, const pnrt_denoise_variance_params* params) {
@@ -2169,7 +2147,7 @@ int pnrt_denoise_variance(pnrt_ctx* c, const pnrt_denoise_variance_params* param
                                         "environment or traversal mode changed): render_guides again");
     if (int rc = check_fault(c)) return rc;      // completed work that faulted
     HIPCHK(c, hipSetDevice(c->device));
-    return denoise_variance(c, p);
+    return denoise_run<true>(c, p.levels, p.sigma_variance, p.sigma_normal, p.sigma_position);
 }
 
 int pnrt_read_denoised(pnrt_ctx* c, float* out) {

@@ -39,43 +39,8 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, PT_PRIM_WF_WAVES) pt_camera_ra
         TravState t;
         t.r = make_ray(eye, dir, fp.mode);
         t.tMax = PT_FLOAT_MAX;
-        t.hitTri = -1; t.lt = 0; t.lc = 0;
-        t.spa = (uint32_t)threadIdx.x * 8u;
-        t.cur = REF_NONE;
         t.rid = 2u << 30;       // closest hit
-        float zlo;
-        if (mine && box_fast(t.r, s.root_min[0], s.root_min[1], s.root_min[2], s.root_max[0], s.root_max[1],
-                             s.root_max[2], zlo)) {
-            t.cur = s.root_ref;
-            if (t.cur & REF_LEAF) { if (TBL) decode_leaf(s, t.cur, t.lt, t.lc); else t.lt = (int)t.cur; t.cur = REF_NONE; }
-        }
-        int busy = mine && (t.cur != REF_NONE || wf_has_tri<TBL>(t));
-        auto run = [&](auto ident_tag) {
-            constexpr bool ID = decltype(ident_tag)::value;
-            for (;;) {
-                if (wf_step<STK, ID, TBL>(s, b, geo, lds, t)) busy = 0;     // (a finished lane's step is a no-op)
-                if (__ballot(busy != 0) == 0) break;
-            }
-        };
-        if (__ballot(busy != 0 && t.r.kz() != 2) == 0) run(std::true_type{});
-        else run(std::false_type{});
-        if (!mine) continue;
-        float4 q0, q1, q2;
-        if (t.hitTri != -1) {
-            Hit h = make_hit(s, t.r, wf_tri_index<TBL>(t.hitTri));
-            f3 em = get_emissive(s, h.mat);
-            q0 = make_float4(h.P.x, h.P.y, h.P.z, __int_as_float((h.mat & 0x00ffffff) | ((h.tex + 1) << 24)));
-            q1 = make_float4(h.N.x, h.N.y, h.N.z, h.u);
-            q2 = make_float4(h.v, em.x, em.y, em.z);
-        } else {
-            f3 c = env_color(s, dir);
-            q0 = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-            q1 = make_float4(0.f, 0.f, 0.f, 0.f);
-            q2 = make_float4(0.f, c.x, c.y, c.z);
-        }
-        const size_t at = PT_CHECK(b.fault, i, n, PT_SITE_PRIMARY);
-        rec[3 * at] = q0;
-        rec[3 * at + 1] = q1;
-        rec[3 * at + 2] = q2;
+        wf_trace_closest<STK, TBL>(s, b, geo, lds, t, mine);
+        if (mine) wf_primary_record<TBL>(s, t, dir, rec + 3 * PT_CHECK(b.fault, i, n, PT_SITE_PRIMARY));
     }
 }

@@ -1875,6 +1875,61 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, CC ? WF_TRACE_WAVES_CC : WF_TR
 #ifndef PT_PRIM_WF_WAVES
 #define PT_PRIM_WF_WAVES 7
 #endif
+// A ray's entry at the root, from a ready t.r, t.tMax and t.rid: no hit, nothing pending,
+// the lane's empty stack, then -- where `go` -- the root box test that opens BVHIntersect in
+// the reference's ray_tracing.comp, and a root leaf's decode.  Returns whether the lane has
+// anything to step.
+template <bool TBL>
+PN_DEV int wf_root_entry(const DevScene& s, TravState& t, bool go) {
+    float zlo;
+    uint32_t root = REF_NONE;
+    int nlt = 0, nlc = 0;
+    if (go && box_fast(t.r, s.root_min[0], s.root_min[1], s.root_min[2], s.root_max[0], s.root_max[1], s.root_max[2], zlo)) {
+        root = s.root_ref;
+        if (root & REF_LEAF) { if (TBL) decode_leaf(s, root, nlt, nlc); else nlt = (int)root; root = REF_NONE; }
+    }
+    t.hitTri = -1; t.lt = nlt; t.lc = nlc;
+    t.spa = (uint32_t)threadIdx.x * 8u;
+    t.cur = root;
+    return go && (t.cur != REF_NONE || wf_has_tri<TBL>(t));
+}
+// The wave traces its lanes' closest-hit rays (t.r, t.tMax, t.rid set; `go`: the lane has
+// one) to their ends: every lane steps until no lane of the wave is busy.
+template <int STK, bool TBL>
+PN_DEV void wf_trace_closest(const DevScene& s, const WfBufs& b, __amdgpu_buffer_rsrc_t geo, uint2* lds, TravState& t,
+                             bool go) {
+    int busy = wf_root_entry<TBL>(s, t, go);
+    auto run = [&](auto ident_tag) {
+        constexpr bool ID = decltype(ident_tag)::value;
+        for (;;) {
+            if (wf_step<STK, ID, TBL>(s, b, geo, lds, t)) busy = 0;     // (a finished lane's step is a no-op)
+            if (__ballot(busy != 0) == 0) break;
+        }
+    };
+    if (__ballot(busy != 0 && t.r.kz() != 2) == 0) run(std::true_type{});
+    else run(std::false_type{});
+}
+// The camera ray's record (above) of a finished t, at rec[0..2].  dir: the ray's direction.
+template <bool TBL>
+PN_DEV void wf_primary_record(const DevScene& s, const TravState& t, f3 dir, float4* rec) {
+    float4 q0, q1, q2;
+    if (t.hitTri != -1) {
+        Hit h = make_hit(s, t.r, wf_tri_index<TBL>(t.hitTri));
+        f3 em = get_emissive(s, h.mat);
+        q0 = make_float4(h.P.x, h.P.y, h.P.z, __int_as_float((h.mat & 0x00ffffff) | ((h.tex + 1) << 24)));
+        q1 = make_float4(h.N.x, h.N.y, h.N.z, h.u);
+        q2 = make_float4(h.v, em.x, em.y, em.z);
+    } else {
+        f3 c = env_color(s, dir);
+        q0 = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+        q1 = make_float4(0.f, 0.f, 0.f, 0.f);
+        q2 = make_float4(0.f, c.x, c.y, c.z);
+    }
+    rec[0] = q0;
+    rec[1] = q1;
+    rec[2] = q2;
+}
+
 template <int STK, bool TBL>
 __global__ void __launch_bounds__(WF_TRACE_BLOCK, PT_PRIM_WF_WAVES) pt_primary_wf(DevScene s, FrameParams fp, WfBufs b,
                                                                                float4* rec) {
@@ -1892,43 +1947,9 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, PT_PRIM_WF_WAVES) pt_primary_w
         TravState t;
         t.r = make_ray(eye, dir, fp.mode);
         t.tMax = PT_FLOAT_MAX;
-        t.hitTri = -1; t.lt = 0; t.lc = 0;
-        t.spa = (uint32_t)threadIdx.x * 8u;
-        t.cur = REF_NONE;
         t.rid = 2u << 30;       // closest hit
-        float zlo;
-        if (mine && box_fast(t.r, s.root_min[0], s.root_min[1], s.root_min[2], s.root_max[0], s.root_max[1],
-                             s.root_max[2], zlo)) {
-            t.cur = s.root_ref;
-            if (t.cur & REF_LEAF) { if (TBL) decode_leaf(s, t.cur, t.lt, t.lc); else t.lt = (int)t.cur; t.cur = REF_NONE; }
-        }
-        int busy = mine && (t.cur != REF_NONE || wf_has_tri<TBL>(t));
-        auto run = [&](auto ident_tag) {
-            constexpr bool ID = decltype(ident_tag)::value;
-            for (;;) {
-                if (wf_step<STK, ID, TBL>(s, b, geo, lds, t)) busy = 0;     // (a finished lane's step is a no-op)
-                if (__ballot(busy != 0) == 0) break;
-            }
-        };
-        if (__ballot(busy != 0 && t.r.kz() != 2) == 0) run(std::true_type{});
-        else run(std::false_type{});
-        if (!mine) continue;
-        float4 q0, q1, q2;
-        if (t.hitTri != -1) {
-            Hit h = make_hit(s, t.r, wf_tri_index<TBL>(t.hitTri));
-            f3 em = get_emissive(s, h.mat);
-            q0 = make_float4(h.P.x, h.P.y, h.P.z, __int_as_float((h.mat & 0x00ffffff) | ((h.tex + 1) << 24)));
-            q1 = make_float4(h.N.x, h.N.y, h.N.z, h.u);
-            q2 = make_float4(h.v, em.x, em.y, em.z);
-        } else {
-            f3 c = env_color(s, dir);
-            q0 = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-            q1 = make_float4(0.f, 0.f, 0.f, 0.f);
-            q2 = make_float4(0.f, c.x, c.y, c.z);
-        }
-        rec[3 * i] = q0;
-        rec[3 * i + 1] = q1;
-        rec[3 * i + 2] = q2;
+        wf_trace_closest<STK, TBL>(s, b, geo, lds, t, mine);
+        if (mine) wf_primary_record<TBL>(s, t, dir, rec + 3 * i);
     }
 }
 

@@ -9,6 +9,7 @@ product library itself is built by the session fixture.
   pipes1           one call in flight (the census build's -DWF_PIPES=1)
   tunables         trace block 128 / 512, LDS stack depth 12, refill threshold,
                    grid caps, frames per batch, call staggering off / other points
+  dn_cached        both denoisers with every level's taps through the caches
 """
 import concurrent.futures
 import os
@@ -32,13 +33,13 @@ VARIANTS = {
                  "-DWF_MAX_CHUNK_FRAMES=8", "-DWF_QSHARDS=8", "-DWF_KIND_ORDER=0x012"],
     "nostagger": ["-DWF_STAGGER=0"],
     "stagger": ["-DWF_STAGGER=5", "-DWF_STAGGER_PATHS=4000000", "-DWF_TRACE_GRID_PCT_ONE=90"],
+    "dn_cached": ["-DDN_LDS_MAX_STEP=0"],
 }
 
 
 def _compile(name, flags, out_dir):
-    cmd = [build.HIPCC, f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-           "-fno-slp-vectorize", "-fno-gpu-rdc", "--cuda-device-only", "-c", "-I", build.INC, *flags,
-           os.path.join(build.CSRC, "pnrt_device.hip"), "-o", os.path.join(out_dir, f"{name}.o")]
+    # build.py's device recipe (its -fPIC -shared are unused here), device code only
+    cmd = build.device_cmd(os.path.join(out_dir, f"{name}.o"), ["--cuda-device-only", "-c", *flags], src_hash="switch")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     return name, r.returncode, r.stderr[-2000:]
 

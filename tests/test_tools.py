@@ -1,7 +1,8 @@
 """The measurement tools that tie the committed profiles to the bench lines
 (CPU): prof_summary.py (rocprof kernel trace vs a line's kernel_ms, the sizing
 call excluded) and record_pmc.py (an N = 1 line's traffic -> profiles/pmc.json
-for N > 1 lines), on synthetic inputs."""
+for N > 1 lines), on synthetic inputs; and isa_diff.py, which vouches for kernels a
+refactor must not change, on hand-written assembly."""
 import csv
 import json
 import os
@@ -42,6 +43,46 @@ def test_prof_summary_excludes_the_sizing_call(tmp_path):
     r = json.load(open(out))
     assert r["kernels"]["trace"]["launches"] == 12 and r["kernels"]["trace"]["launches_after_sizing_call"] == 8
     assert abs(r["check"]["rel_diff"]) < 1e-6 and r["check"]["compared_with"] == "kernel_ms"
+
+
+_ASM = """\t.text
+_Z1kv:                                  ; @_Z1kv
+; %bb.0:
+\ts_load_dword s0, s[0:1], 0x0
+{body}
+.LBB0_1:                                ; a label, numbered
+\ts_cbranch_execz .LBB0_1
+\ts_endpgm
+.Lfunc_end0:
+\t.size\t_Z1kv, .Lfunc_end0-_Z1kv
+"""
+
+
+def test_isa_diff_tells_same_reordered_and_changed():
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import isa_diff
+    mov, add = "\tv_mov_b32_e32 v1, 0        ; comment", "\tv_add_f32_e32 v2, v0, v0"
+    old = isa_diff.kernels(_ASM.format(body=mov + "\n" + add).splitlines())
+    assert old["_Z1kv"] == ["s_load_dword s0, s[0:1], 0x0", "v_mov_b32_e32 v1, 0", "v_add_f32_e32 v2, v0, v0", "LBB:",
+                            "s_cbranch_execz LBB", "s_endpgm"]
+    # the same stream under other label numbers and comments
+    same = isa_diff.kernels(_ASM.format(body=mov.split(";")[0] + "\n" + add).replace("LBB0_1", "LBB7_3").splitlines())
+    rep, bad = isa_diff.compare(old, same)
+    assert bad == 0 and len(rep) == 1 and rep[0].startswith("same ")
+    # two instructions swapped: the same multiset, and the diff says which moved
+    rep, bad = isa_diff.compare(old, isa_diff.kernels(_ASM.format(body=add + "\n" + mov).splitlines()))
+    assert bad == 1 and rep[0].startswith("REORDERED ") and "VALU 2 -> 2" in rep[0]
+    assert any(x.strip().startswith("-v_mov_b32") or x.strip().startswith("-v_add_f32") for x in rep[1:])
+    # one instruction replaced: not the same work
+    rep, bad = isa_diff.compare(old, isa_diff.kernels(_ASM.format(body=mov + "\n\tv_mul_f32_e32 v2, v0, v0").splitlines()))
+    assert bad == 1 and rep[0].startswith("DIFFERENT ")
+    assert "    -v_add_f32_e32 v2, v0, v0" in rep and "    +v_mul_f32_e32 v2, v0, v0" in rep
+    # a long diff is capped, a renamed kernel is found through the name map, a missing one is listed
+    many = isa_diff.kernels(_ASM.format(body="\n".join(f"\tv_mov_b32_e32 v{i}, 0" for i in range(200))).splitlines())
+    rep, bad = isa_diff.compare(old, {"_Z2k2v": many["_Z1kv"]}, {"_Z1kv": "_Z2k2v"})
+    assert bad == 1 and len(rep) == 1 + isa_diff.DIFF_LINES + 1 and "more diff lines" in rep[-1]
+    rep, bad = isa_diff.compare(old, {"_Z2k2v": many["_Z1kv"]})
+    assert bad == 0 and rep == ["only in old: _Z1kv", "only in new: _Z2k2v"]
 
 
 def test_record_pmc_keys_by_source_hash(tmp_path, monkeypatch):

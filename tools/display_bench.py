@@ -34,10 +34,7 @@ VARIANT = os.path.join(build.PKG, "variants", "libpnrt_histwave.so")
 
 def build_variant():
     os.makedirs(os.path.dirname(VARIANT), exist_ok=True)
-    subprocess.run([build.HIPCC, f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                    "-fno-fast-math", "-fno-gpu-rdc", "-fno-slp-vectorize", f'-DPNRT_SRC_HASH="{build.device_source_hash()}"',
-                    "-DLUMA_HIST_PER_WAVE=1", "-I", build.INC, *[os.path.join(build.CSRC, s) for s in build.DEVICE_SRCS],
-                    "-o", VARIANT], check=True)
+    subprocess.run(build.device_cmd(VARIANT, ["-DLUMA_HIST_PER_WAVE=1"]), check=True)
     print(VARIANT)
 
 

@@ -6,15 +6,23 @@ must not change the product kernels:
     tools/isa_diff.py old.s new.s [name-map old=new ...]
 
 Comments, directives and basic-block label numbers are normalised away; a
-kernel whose instruction stream is identical prints "same".  Kernels present
-on one side only are listed.  Exit status 1 when any common kernel differs."""
+kernel whose instruction stream is identical prints "same".  One that differs
+prints "REORDERED" when the two streams are the same multiset of instructions
+(the same work in another order), "DIFFERENT" otherwise, and then the unified
+diff of the two normalised streams, at most DIFF_LINES lines of it.  Kernels
+present on one side only are listed.  Exit status 1 when any common kernel
+is not "same"."""
+import collections
+import difflib
 import re
 import sys
 
+DIFF_LINES = 40
 
-def kernels(path):
+
+def kernels(lines):
     out, cur, body = {}, None, []
-    for line in open(path):
+    for line in lines:
         m = re.match(r"^(_Z\w+|[A-Za-z_]\w*):\s*(;.*)?$", line)
         if m and not line.startswith(".L"):
             cur, body = m.group(1), []
@@ -34,24 +42,36 @@ def kernels(path):
     return out
 
 
-def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-    rename = dict(x.split("=", 1) for x in sys.argv[3:])
-    bad = 0
+def compare(a, b, rename=None):
+    """The report's lines and the number of common kernels that are not the same."""
+    rename = rename or {}
+    rep, bad = [], 0
     for k in sorted(a):
         kb = rename.get(k, k)
         if kb not in b:
-            print(f"only in old: {k}")
+            rep.append(f"only in old: {k}")
             continue
         if a[k] == b[kb]:
-            print(f"same      {len(a[k]):6d} lines  {k[:90]}")
-        else:
-            bad += 1
-            va = sum(1 for x in a[k] if x.startswith("v_"))
-            vb = sum(1 for x in b[kb] if x.startswith("v_"))
-            print(f"DIFFERENT {len(a[k]):6d} -> {len(b[kb]):6d} lines, VALU {va} -> {vb}  {k[:90]}")
+            rep.append(f"same      {len(a[k]):6d} lines  {k[:90]}")
+            continue
+        bad += 1
+        va = sum(1 for x in a[k] if x.startswith("v_"))
+        vb = sum(1 for x in b[kb] if x.startswith("v_"))
+        word = "REORDERED" if collections.Counter(a[k]) == collections.Counter(b[kb]) else "DIFFERENT"
+        rep.append(f"{word} {len(a[k]):6d} -> {len(b[kb]):6d} lines, VALU {va} -> {vb}  {k[:90]}")
+        diff = list(difflib.unified_diff(a[k], b[kb], "old", "new", n=1, lineterm=""))
+        rep += ["    " + x for x in diff[:DIFF_LINES]]
+        if len(diff) > DIFF_LINES:
+            rep.append(f"    ... {len(diff) - DIFF_LINES} more diff lines")
     for k in sorted(set(b) - {rename.get(x, x) for x in a}):
-        print(f"only in new: {k}")
+        rep.append(f"only in new: {k}")
+    return rep, bad
+
+
+def main():
+    a, b = kernels(open(sys.argv[1])), kernels(open(sys.argv[2]))
+    rep, bad = compare(a, b, dict(x.split("=", 1) for x in sys.argv[3:]))
+    print("\n".join(rep))
     return 1 if bad else 0
 
 

@@ -41,10 +41,7 @@ def main():
     sys.path.insert(0, root)
     from pnraytracing_amd import build
     with tempfile.TemporaryDirectory() as tmp:
-        cmd = [build.HIPCC, f"--offload-arch={build.ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-               "-fno-fast-math", "-fno-gpu-rdc", "-fno-slp-vectorize", '-DPNRT_SRC_HASH="listing"', "-I", build.INC,
-               "-Rpass-analysis=kernel-resource-usage", *[os.path.join(build.CSRC, s) for s in build.DEVICE_SRCS],
-               "-o", os.path.join(tmp, "libpnrt.so")]
+        cmd = build.device_cmd(os.path.join(tmp, "libpnrt.so"), ["-Rpass-analysis=kernel-resource-usage"], src_hash="listing")
         err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
     kernels, cur = {}, None
     for line in err.split("\n"):
