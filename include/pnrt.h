@@ -276,6 +276,103 @@ int pnrt_render_cameras(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames, 
 int pnrt_cameras_batch_plan(pnrt_ctx* ctx, uint32_t n_frames, int band_rows, int n_shards, int shard,
                             uint32_t* frames_per_batch, uint32_t* n_batches, int64_t* batch_bytes);
 
+/* Caller ray buffers (not in the reference, whose CameraGetRay is a pinhole): the image
+ * whose pixel (x, y) of frame first_frame + k starts from a ray the caller supplies --
+ * what ray_tracing.comp renders there when CameraGetRay returns Ray(origin, direction):
+ * the camera ray, the miss colour of its direction, V = -direction at bounce 0 and
+ * everything downstream.  The seed, the Sobol index, the blend weight
+ * 1 / (float)(frame + 1), the clamp, the frame order, the selector and the traversal
+ * mode are pnrt_render's.  Any camera model, per-pixel jitter, lens or motion sample is
+ * a choice of rays (pnrt_make_rays below makes four models' on the device).
+ *
+ * rays_dev: device memory of the context's device, 16-byte aligned, one pnrt_ray per
+ * pixel of the WHOLE image whatever the selector; the ray of pixel (x, y) is record
+ * y * width + x, row 0 = bottom.  frame_stride counts records: frame first_frame + k
+ * reads the set that starts at record k * frame_stride; 0 (one set serves every
+ * frame: a camera model) or >= width * height (a set per frame).  The direction is used
+ * as given, never normalised: only unit directions are meaningful, any finite one is
+ * memory-safe.  reserved0 / reserved1 are never read.
+ * A record with a non-finite float among its six, or a direction of three zeros, is
+ * "no ray" (pnrt_query_rays' rule): that pixel's colour for that frame is (0, 0, 0),
+ * blended and folded into the moments like any other frame colour; no path starts.
+ *
+ * The pnrt_set_frame camera is ignored and stays current for pnrt_render,
+ * pnrt_render_guides and pnrt_reproject; the kept per-pixel camera-ray records are
+ * neither used nor invalidated.  Asynchronous; the buffer is not copied: every batch's
+ * reads are ordered after everything queued on the context's stream at the time of the
+ * call (whichever worker stream runs the batch), and the caller keeps the buffer
+ * unchanged until the call's work has completed.  Batches, PNRT_BATCH_BYTES, moments
+ * and profile classes are pnrt_render_cameras' (the same 48-byte record per path slot;
+ * pnrt_cameras_batch_plan reports the plan; batch b, frame slot k reads set
+ * b * frames_per_batch + k; the ray launch is PNRT_K_PRIMARY).
+ *
+ * Errors (nothing queued, accumulation untouched): PNRT_E_STATE before
+ * pnrt_upload_scene or pnrt_set_frame, or under PNRT_KERNEL_V1; PNRT_E_ARG for
+ * rays_dev == NULL with n_frames > 0, a pointer that is not 16-byte aligned,
+ * frame_stride < 0 or in 1 .. width * height - 1 or so large that the last set's end
+ * passes 2^63 bytes, a bad selector,
+ * first_frame + n_frames > 0xFFFFFFFF; PNRT_E_TRACE as pnrt_render.  n_frames == 0 or a
+ * shard without rows: PNRT_OK, nothing queued.
+ * Out of scope: an adaptive variant, pnrt_reproject across ray sets, a host-array form,
+ * a tMax or near clip per ray. */
+typedef struct { float origin[3], reserved0, direction[3], reserved1; } pnrt_ray;   /* 32 bytes */
+int pnrt_render_rays(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames, const void* rays_dev, int64_t frame_stride,
+                     int band_rows, int n_shards, int shard);
+/* pnrt_render_guides with the camera rays taken from one set of width * height records
+ * (alignment and state errors as above): always the whole image, asynchronous and
+ * ordered like pnrt_render_rays; one PNRT_K_PRIMARY launch into the guides' own record
+ * buffer, then the guide images.  A no-ray pixel is a miss whose albedo is 0.  These
+ * guides carry no camera: they stay valid -- pnrt_denoise, pnrt_denoise_variance,
+ * pnrt_read_aov and pnrt_aov_device_ptr accept them; that they match the accumulation
+ * is the caller's statement -- until pnrt_render_guides or pnrt_reproject replaces them
+ * or the frame size, the scene or the traversal mode changes.  pnrt_reproject never
+ * uses them as `from`'s guides: it renders its own. */
+int pnrt_render_guides_rays(pnrt_ctx* ctx, const void* rays_dev);
+
+/* A ray generator on the device: n_sets sets (frames first_frame ..) of the current
+ * frame size into rays_dev_out (alignment and stride rules as above; gap records
+ * between sets are left untouched; with frame_stride 0 the sets coincide and the one of
+ * first_frame is written).  Asynchronous on the context's stream, class PNRT_K_BLEND.
+ * With s = px / width, t = py / height (the reference's sample point):
+ *   PNRT_CAM_PINHOLE   origin eye, direction CameraGetRay's operations in its order:
+ *                      without jitter and lens pnrt_render_rays on these rays is
+ *                      pnrt_render, bit for bit
+ *   PNRT_CAM_ORTHO     origin (lower_left + s * horizontal) + t * vertical, direction
+ *                      f = normalize(cross(vertical, horizontal))
+ *   PNRT_CAM_EQUIRECT  origin eye; r = normalize(horizontal), u = normalize(vertical);
+ *                      phi = (s - 0.5) * 2 pi, theta = (t - 0.5) * pi; direction
+ *                      normalize((cos theta sin phi) r + sin theta u + (cos theta cos phi) f)
+ *   PNRT_CAM_FISHEYE   equidistant, fov_deg in (0, 360]: a = 2s - 1, b = 2t - 1,
+ *                      rho = sqrt(a^2 + b^2); rho > 1: no ray (a record of zeros);
+ *                      rho == 0: f; else theta = rho * fov / 2, direction
+ *                      normalize(sin theta ((a / rho) r + (b / rho) u) + cos theta f)
+ * Samples: u_i = (float)(((n * A_i + h_i) & 0xFFFFFFFF) >> 8) * 2^-24, n = frame + 1, A
+ * pnrt_camera_sequence's constants; per_pixel 0: h_i = 0 (the per-frame samples);
+ * per_pixel 1: h_i = wang_hash of the seed 4 * (py * width + px) + i, so every pixel
+ * walks its own rotation of the sequence.  aa_width > 0 shifts (s, t) by
+ * ((u_0 - 0.5) * aa_width / width, (u_1 - 0.5) * aa_width / height), any model;
+ * lens_radius > 0 is pnrt_camera_sequence's thin lens (u_2, u_3), PNRT_CAM_PINHOLE only.
+ * All arithmetic is binary32, every operation rounded on its own, in the order of
+ * DESIGN.md section 29.
+ * PNRT_E_ARG: an unknown model, a non-finite camera float, fov_deg outside its range
+ * (fisheye), a negative or non-finite aa_width or lens_radius, a lens with another
+ * model or with focus_distance not > 0, per_pixel not 0 or 1, reserved != 0, the
+ * buffer rules above.  PNRT_E_STATE before pnrt_set_frame. */
+#define PNRT_CAM_PINHOLE 0
+#define PNRT_CAM_ORTHO 1
+#define PNRT_CAM_EQUIRECT 2
+#define PNRT_CAM_FISHEYE 3
+typedef struct {
+    int model;                 /* PNRT_CAM_* */
+    pnrt_camera camera;        /* eye, lower_left, horizontal, vertical */
+    float fov_deg;             /* PNRT_CAM_FISHEYE */
+    float aa_width, lens_radius, focus_distance;   /* as pnrt_lens_params */
+    int per_pixel;             /* 0 or 1 */
+    int reserved;              /* must be 0 */
+} pnrt_ray_camera;             /* 76 bytes */
+int pnrt_make_rays(pnrt_ctx* ctx, const pnrt_ray_camera* cam, uint32_t first_frame, uint32_t n_sets, void* rays_dev_out,
+                   int64_t frame_stride);
+
 /* Redraw semantics (main.cpp:592-596): zero the accumulation image.  Waits
  * for the calls in flight first, and clears a PNRT_E_TRACE fault. */
 int pnrt_reset_accum(pnrt_ctx* ctx);

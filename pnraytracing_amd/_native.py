@@ -161,6 +161,22 @@ class LensParams(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+CAM_MODELS = ("pinhole", "ortho", "equirect", "fisheye")   # PNRT_CAM_* order
+
+
+class Ray(ctypes.Structure):
+    """``pnrt_ray`` (32 bytes)."""
+    _fields_ = [("origin", ctypes.c_float * 3), ("reserved0", ctypes.c_float), ("direction", ctypes.c_float * 3),
+                ("reserved1", ctypes.c_float)]
+
+
+class RayCamera(ctypes.Structure):
+    """``pnrt_ray_camera`` (76 bytes)."""
+    _fields_ = [("model", ctypes.c_int), ("camera", Camera), ("fov_deg", ctypes.c_float), ("aa_width", ctypes.c_float),
+                ("lens_radius", ctypes.c_float), ("focus_distance", ctypes.c_float), ("per_pixel", ctypes.c_int),
+                ("reserved", ctypes.c_int)]
+
+
 QUERY_CLOSEST, QUERY_ANY = 0, 1                # PNRT_QUERY_*
 
 
@@ -261,6 +277,9 @@ def _type_device(lib):
     _sig(lib, "pnrt_render_cameras", INT, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(Camera), INT, INT, INT)
     _sig(lib, "pnrt_cameras_batch_plan", INT, P, ctypes.c_uint32, INT, INT, INT, ctypes.POINTER(ctypes.c_uint32),
          ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int64))
+    _sig(lib, "pnrt_render_rays", INT, P, ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_int64, INT, INT, INT)
+    _sig(lib, "pnrt_render_guides_rays", INT, P, P)
+    _sig(lib, "pnrt_make_rays", INT, P, ctypes.POINTER(RayCamera), ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_int64)
 
 
 def fptr(a) -> ctypes.POINTER(ctypes.c_float):

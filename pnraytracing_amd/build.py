@@ -29,7 +29,7 @@ ROCM = "/opt/rocm"             # headers and libraries of the HIP runtime and RC
 DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
                "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pt_adaptive.h", "pt_query.h", "pn_math.h",
-               "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h", "pt_display.h", "pt_refit.h", "pt_cameras.h"]
+               "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h", "pt_display.h", "pt_refit.h", "pt_cameras.h", "pt_rays.h"]
 
 
 def _run(cmd, cwd=None):
@@ -136,6 +136,8 @@ ABI_CALLERS = {
     "c_abi_refit.c": [],
     # a camera sequence (pnrt_camera_sequence) rendered with pnrt_render_cameras (tests/test_gpu_cameras.py)
     "c_abi_cameras.c": ["-lpnrt_host", "-lm"],
+    # a fisheye ray set (pnrt_make_rays) rendered with pnrt_render_rays and pnrt_render_guides_rays (tests/test_gpu_rays_c_abi.py)
+    "c_abi_rays.c": ["-lamdhip64"],
 }
 
 
@@ -168,7 +170,7 @@ def build_abi_caller(force=False):
             os.path.join(PKG, "libpnrt.so"), os.path.join(PKG, "libpnrt_host.so")]
     if not all(os.path.exists(d) for d in need):
         return None
-    outs = [_abi_caller(source, force) for source in ABI_CALLERS if source not in ("c_abi_refit.c", "c_abi_cameras.c")]
+    outs = [_abi_caller(source, force) for source in ABI_CALLERS if source not in ("c_abi_refit.c", "c_abi_cameras.c", "c_abi_rays.c")]
     return outs[0]
 
 
@@ -178,6 +180,10 @@ def build_refit_abi_caller(force=False):
 
 def build_cameras_abi_caller(force=False):
     return _abi_caller("c_abi_cameras.c", force)
+
+
+def build_rays_abi_caller(force=False):
+    return _abi_caller("c_abi_rays.c", force)
 
 
 def build_oracle(force=False):
@@ -195,6 +201,7 @@ def build_all(force=False):
     build_abi_caller(force)
     build_refit_abi_caller(force)
     build_cameras_abi_caller(force)
+    build_rays_abi_caller(force)
     build_oracle(force)
 
 

@@ -30,6 +30,7 @@
 #include "pt_display.h"
 #include "pt_refit.h"
 #include "pt_cameras.h"
+#include "pt_rays.h"
 
 __global__ void pt_pack_rows_kernel(const float4* accum, float4* dst, int width, int rows, int band,
                                     int n_shards, int shard) {
@@ -189,6 +190,7 @@ struct pnrt_ctx {
         hipStream_t w = nullptr;
         hipEvent_t ev_join = nullptr, ev_blend = nullptr;
         hipEvent_t ev_stage = nullptr;   // WF_STAGGER: the call has reached its drain-heavy end
+        hipEvent_t ev_rays = nullptr;    // pnrt_render_rays: the context stream at the time of the call
         bool stage_set = false;
         DevBuf<float4> primary;
         PrimKey prim;
@@ -196,7 +198,7 @@ struct pnrt_ctx {
         DevBuf<char> wf;
         DevBuf<uint2> ovf;
         bool blend_pending = false;  // ev_blend guards the colour buffer's last reader
-        // pnrt_render_cameras: the batch's camera-ray record per path slot and its camera table
+        // pnrt_render_cameras / pnrt_render_rays: the batch's camera-ray record per path slot; the camera table
         DevBuf<float4> camrec;
         DevBuf<float> camtab;
     };
@@ -231,6 +233,7 @@ struct pnrt_ctx {
         float cam[12] = {};
         int width = 0, height = 0, mode = -1;
         bool valid = false;
+        bool rays = false;  // rendered from a caller's ray set (pnrt_render_guides_rays): they carry no camera
     };
     uint64_t tex_epoch = 1;                // bumped by pnrt_upload_texture (the albedo image reads the textures)
     DevBuf<float4> aov[PNRT_AOV_COUNT];
@@ -569,7 +572,8 @@ static int report_trace_diag(pnrt_ctx* c, const WfBufs& b, hipStream_t st, int b
 static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const WfLayout& L, hipStream_t st,
                         const float4* primary, float4* colors, bool alone, bool one, hipEvent_t stage = nullptr,
                         const WfAdapt* ad = nullptr,       // ad: an adaptive batch's slots (pt_adaptive.h)
-                        const WfCams* cm = nullptr) {      // cm: a camera batch's table (pt_cameras.h; primary = its records)
+                        const WfCams* cm = nullptr,        // cm: a camera batch's table (pt_cameras.h; primary = its records)
+                        const WfRays* ry = nullptr) {      // ry: a ray batch's rays (pt_rays.h; primary = its records)
     WfBufs b = L.b;
     if (b.n > WF_META_SLOT) return set_err(c, PNRT_E_ARG, "render: too many paths per batch");
     // the cooperative finish of closest-hit rays pays where the drain leaves the chip
@@ -586,6 +590,7 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
         ProfScope ps(c, PNRT_K_GEN, st);
         if (ad) hipLaunchKernelGGL(pt_wf_gen_setup<WfAdapt>, g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
         else if (cm) hipLaunchKernelGGL(pt_wf_gen_setup<WfCams>, g, dim3(256), 0, st, s, fp, b, primary, colors, *cm);
+        else if (ry) hipLaunchKernelGGL(pt_wf_gen_setup<WfRays>, g, dim3(256), 0, st, s, fp, b, primary, colors, *ry);
         else hipLaunchKernelGGL(pt_wf_gen_setup<>, g, dim3(256), 0, st, s, fp, b, primary, colors);
     }
     HIPCHK(c, hipGetLastError());
@@ -629,6 +634,10 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
                 hipLaunchKernelGGL((pt_wf_shade_setup<true, WfCams>), g, dim3(256), 0, st, s, fp, b, primary, colors, *cm);
             else if (cm)
                 hipLaunchKernelGGL((pt_wf_shade_setup<false, WfCams>), g, dim3(256), 0, st, s, fp, b, primary, colors, *cm);
+            else if (ry && fin)
+                hipLaunchKernelGGL((pt_wf_shade_setup<true, WfRays>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ry);
+            else if (ry)
+                hipLaunchKernelGGL((pt_wf_shade_setup<false, WfRays>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ry);
             else if (fin)
                 hipLaunchKernelGGL(pt_wf_shade_setup<true>, g, dim3(256), 0, st, s, fp, b, primary, colors);
             else
@@ -691,6 +700,7 @@ static int pipes_init(pnrt_ctx* c) {
         HIPCHK(c, hipEventCreateWithFlags(&P.ev_join, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&P.ev_blend, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&P.ev_stage, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&P.ev_rays, hipEventDisableTiming));
     }
     return PNRT_OK;
 }
@@ -825,6 +835,8 @@ struct BatchRoute {
     int ovf_stride, tiles_x;
     const WfAdapt* ad;       // an adaptive call's active-tile list, or null
     const float* cams;       // pnrt_render_cameras: the call's cameras (pinned host memory, 12 floats per frame), or null
+    const float4* rays;      // pnrt_render_rays: the call's first set (device memory), or null,
+    int64_t ray_stride;      // and the records between the sets of consecutive frames
 };
 // The batches of one call on pipe P: per group of `chunk` frames one batch (gen ->
 // {trace -> shade} x depth) of per_frame path slots per frame on R.w, then the
@@ -861,8 +873,23 @@ static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pn
                 hipLaunchKernelGGL((pt_camera_rays_wf<WF_STACK, false>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, cm, P.camrec);
             HIPCHK(c, hipGetLastError());
         }
+        WfRays ry{nullptr, 0};
+        if (R.rays) {
+            // the batch's camera rays from the caller's sets f0 .. f0 + cf - 1: one per path slot (pt_rays.h), behind the
+            // previous batch's kernels on w, the last readers of the records
+            ry.rays = R.rays + 2 * ((size_t)f0 * (size_t)R.ray_stride);
+            ry.frame_stride = R.ray_stride;
+            primary = P.camrec;
+            ProfScope ps(c, PNRT_K_PRIMARY, w);
+            const unsigned gp = (unsigned)std::min<size_t>(((size_t)a.b.n + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
+            if (s.has_leaf_table)
+                hipLaunchKernelGGL((pt_rays_wf<WF_STACK, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, ry, P.camrec);
+            else
+                hipLaunchKernelGGL((pt_rays_wf<WF_STACK, false>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, ry, P.camrec);
+            HIPCHK(c, hipGetLastError());
+        }
         if ((rc = render_batch(c, s, fp, a, w, primary, P.colors, R.alone, R.one, R.stagger && last ? P.ev_stage : nullptr,
-                               R.ad, R.cams ? &cm : nullptr)))
+                               R.ad, R.cams ? &cm : nullptr, R.rays ? &ry : nullptr)))
             return rc;
         if (R.stagger && last) P.stage_set = true;
         if (w != c->stream) {
@@ -899,14 +926,16 @@ static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pn
 // cams: pnrt_render_cameras' call -- the cameras of its nf frames in pinned host memory; the batches
 // are planned with the camera-ray records' bytes, trace their own camera rays (run_batches) and
 // leave the pipe's per-pixel records and their key alone.
+// rays: pnrt_render_rays' call -- the caller's device ray sets, ray_stride records apart; planned and
+// buffered like a camera call, and every batch's reads follow what the context stream held at the call.
 static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, uint32_t first, uint32_t nf,
-                            const float* cams = nullptr) {
+                            const float* cams = nullptr, const float4* rays = nullptr, int64_t ray_stride = 0) {
     int rc;
     if ((rc = pipes_init(c))) return rc;
     const size_t pix = (size_t)fp.rows * c->width;
     const int tiles_x = (c->width + 7) / 8;
     const size_t per_frame = frame_paths(c->width, fp.rows);
-    const uint32_t chunk = plan_chunk(c, per_frame, pix, nf, cams ? CAM_REC_BYTES : 0);   // frames per batch
+    const uint32_t chunk = plan_chunk(c, per_frame, pix, nf, cams || rays ? CAM_REC_BYTES : 0);   // frames per batch
     if (chunk == 0) return set_err(c, PNRT_E_ARG, "render: frame too large for one batch");
     // calls in flight by call size (paths per batch): small (< 5M: multi-GPU shares)
     // 4 with > 4 hardware queues; 5M-12M 2 -- their launches are long enough to fill
@@ -944,11 +973,11 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
     // the same size reallocates (a reallocation waits for all calls in flight)
     for (unsigned q = 0; q < npipes; ++q)
         if ((rc = pipe_size(c, c->pipe[(pi + q) % npipes], pix, pix * 16 * chunk, per_frame * chunk, ovf.bytes))) return rc;
-    if (cams)
+    if (cams || rays)
         for (unsigned q = 0; q < npipes; ++q) {
             pnrt_ctx::Pipe& Q = c->pipe[(pi + q) % npipes];
             if ((rc = Q.camrec.reserve(c, per_frame * chunk * CAM_REC_BYTES)) ||
-                (rc = Q.camtab.reserve(c, (size_t)WF_MAX_CHUNK_FRAMES * 48)))
+                (cams && (rc = Q.camtab.reserve(c, (size_t)WF_MAX_CHUNK_FRAMES * 48))))
                 return rc;
         }
     ++c->ncall;
@@ -965,8 +994,12 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
         HIPCHK(c, hipStreamWaitEvent(w, c->pipe[prev_pipe].ev_stage, 0));
     P.stage_set = false;
     // the pipe's primary records: traced now, or still valid from an earlier call (PrimKey)
-    if (!cams && (rc = ensure_primary(c, s, fp, w, P.ovf, ovf.stride, P.primary, P.prim))) return rc;
-    const BatchRoute R = {w, alone, one, stagger, ovf.stride, tiles_x, nullptr, cams};
+    if (!cams && !rays && (rc = ensure_primary(c, s, fp, w, P.ovf, ovf.stride, P.primary, P.prim))) return rc;
+    if (rays && w != c->stream) {   // the caller's writes of the rays, queued on the context stream, before the worker's reads
+        HIPCHK(c, hipEventRecord(P.ev_rays, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(w, P.ev_rays, 0));
+    }
+    const BatchRoute R = {w, alone, one, stagger, ovf.stride, tiles_x, nullptr, cams, rays, ray_stride};
     if ((rc = run_batches(c, s, fp, P, R, per_frame, chunk, first, nf))) return rc;
     if (cams) {                 // behind the call's last table copy: the staging block is free once it completes
         pnrt_ctx::CamStage& S = c->cam_stage.back();
@@ -994,7 +1027,7 @@ static int render_adaptive(pnrt_ctx* c, const DevScene& s, const FrameParams& fp
     hipStream_t w = (alone && WF_ALONE_ON_CALLER) ? c->stream : P.w;
     P.stage_set = false;
     if ((rc = ensure_primary(c, s, fp, w, P.ovf, ovf.stride, P.primary, P.prim))) return rc;
-    const BatchRoute R = {w, alone, c->serial, false, ovf.stride, (c->width + 7) / 8, &ad, nullptr};
+    const BatchRoute R = {w, alone, c->serial, false, ovf.stride, (c->width + 7) / 8, &ad, nullptr, nullptr, 0};
     return run_batches(c, s, fp, P, R, per_frame, chunk, first, nf);
 }
 
@@ -1031,8 +1064,11 @@ static pnrt_ctx::GuideKey guide_key_for(const pnrt_ctx* c, const pnrt_camera& ca
 }
 // ... for the current camera (pnrt_denoise compares)
 static pnrt_ctx::GuideKey guide_key_now(const pnrt_ctx* c) { return guide_key_for(c, c->cam); }
-static bool guide_key_eq(const pnrt_ctx::GuideKey& a, const pnrt_ctx::GuideKey& b) {
-    return a.valid && b.valid && a.epoch == b.epoch && a.tex_epoch == b.tex_epoch && !std::memcmp(a.cam, b.cam, sizeof a.cam) &&
+// (the guides `a` of a ray set match any camera -- that they match the accumulation is the caller's statement --
+// unless camera-keyed ones are asked for: pnrt_reproject's `from`)
+static bool guide_key_eq(const pnrt_ctx::GuideKey& a, const pnrt_ctx::GuideKey& b, bool camera_keyed = false) {
+    return a.valid && b.valid && a.epoch == b.epoch && a.tex_epoch == b.tex_epoch &&
+           (a.rays ? !camera_keyed : !std::memcmp(a.cam, b.cam, sizeof a.cam)) &&
            a.width == b.width && a.height == b.height && a.mode == b.mode;
 }
 
@@ -1304,7 +1340,7 @@ void pnrt_destroy(pnrt_ctx* c) {
     if (c->stream) (void)sync_all(c);
     for (auto& P : c->pipe) {
         if (P.w) (void)hipStreamDestroy(P.w);
-        for (hipEvent_t e : {P.ev_join, P.ev_blend, P.ev_stage})
+        for (hipEvent_t e : {P.ev_join, P.ev_blend, P.ev_stage, P.ev_rays})
             if (e) (void)hipEventDestroy(e);
     }
     for (auto& S : c->cam_stage)
@@ -2067,6 +2103,132 @@ int pnrt_render_guides(pnrt_ctx* c) {
     return render_guides(c, c->cam);
 }
 
+// ---- caller ray buffers (pt_rays.h) -------------------------------------
+// The buffer rules pnrt_render_rays, pnrt_render_guides_rays and pnrt_make_rays share, for a call over n sets
+// (n == 0: no record is read or written, so NULL passes).
+static_assert(PT_CAM_PINHOLE == PNRT_CAM_PINHOLE && PT_CAM_ORTHO == PNRT_CAM_ORTHO && PT_CAM_EQUIRECT == PNRT_CAM_EQUIRECT &&
+                  PT_CAM_FISHEYE == PNRT_CAM_FISHEYE, "pt_rays.h's models are the header's");
+static int check_ray_buffer(pnrt_ctx* c, const std::string& who, const void* rays, int64_t stride, uint32_t n = 1) {
+    if (!rays && n > 0) return set_err(c, PNRT_E_ARG, who + ": the ray buffer is NULL");
+    if ((uintptr_t)rays & 15u) return set_err(c, PNRT_E_ARG, who + ": the ray buffer must be 16-byte aligned");
+    if (stride < 0 || (stride > 0 && stride < (int64_t)c->width * c->height))
+        return set_err(c, PNRT_E_ARG, who + ": frame_stride must be 0 or >= width * height records");
+    // the last set's end, in bytes, fits 63 bits: no record address wraps
+    const int64_t pix = (int64_t)c->width * c->height, max_records = INT64_MAX / (int64_t)sizeof(pnrt_ray);
+    if (n > 1 && stride > (max_records - pix) / (int64_t)(n - 1))
+        return set_err(c, PNRT_E_ARG, who + ": (n - 1) * frame_stride + width * height records do not fit 63 bits of bytes");
+    return PNRT_OK;
+}
+
+int pnrt_render_rays(pnrt_ctx* c, uint32_t first, uint32_t nf, const void* rays, int64_t stride, int band, int nsh, int shard) {
+    if (!c) return PNRT_E_ARG;
+    if (int rc = need_scene_frame(c, "render_rays")) return rc;
+    if (c->kernel == 1) return set_err(c, PNRT_E_STATE, "render_rays: PNRT_KERNEL_V1 renders the pnrt_set_frame camera only");
+    if (int rc = check_selector(c, "render_rays", band, nsh, shard)) return rc;
+    if (int rc = check_frame_range(c, "render_rays", first, nf)) return rc;
+    if (int rc = check_ray_buffer(c, "render_rays", rays, stride, nf)) return rc;
+    if (int rc = check_fault(c)) return rc;      // an earlier call's trace fault (completed work)
+    if (nf == 0) return PNRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const FrameParams fp = frame_params(c, c->cam, first, nf, band, nsh, shard);
+    if (fp.rows == 0) return PNRT_OK;
+    if (!c->moments_on) c->mom_cover = false;    // frames the moments do not count, as pnrt_render's
+    const DevScene s = launch_scene(c);
+    return render_wavefront(c, s, fp, first, nf, nullptr, static_cast<const float4*>(rays), stride);
+}
+
+int pnrt_render_guides_rays(pnrt_ctx* c, const void* rays) {
+    if (!c) return PNRT_E_ARG;
+    if (int rc = need_scene_frame(c, "render_guides_rays")) return rc;
+    if (int rc = check_ray_buffer(c, "render_guides_rays", rays, 0)) return rc;
+    if (int rc = check_fault(c)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = pipes_init(c)) || (rc = trace_grid_init(c))) return rc;
+    const DevScene s = launch_scene(c);
+    const FrameParams fp = full_frame_params(c, c->cam);     // (the camera floats are not read)
+    const size_t pix = (size_t)c->width * c->height;
+    if (pix > 0xFFFFFFFFull / 64) return set_err(c, PNRT_E_ARG, "render_guides_rays: frame too large");
+    for (int k = 0; k < PNRT_AOV_COUNT; ++k)
+        if ((rc = c->aov[k].reserve(c, pix * 16))) return rc;
+    // the guides' own record buffer and spill area (render_guides), whatever they held
+    const OvfSize ovf = ovf_size(c);
+    if ((rc = c->g_primary.reserve(c, pix * 48)) || (rc = c->g_ovf.reserve(c, ovf.bytes))) return rc;
+    c->g_prim.valid = false;
+    WfBufs pb{};
+    pb.ovf = c->g_ovf;
+    pb.fault = c->fault_dev;
+    pb.ovf_stride = (uint32_t)ovf.stride;
+    pb.n = (uint32_t)frame_paths(c->width, c->height);       // one frame's slots: wf_coords' tiles
+    pb.chunk_frames = 1;
+    pb.tiles_x = (c->width + 7) / 8;
+    const WfRays ry{static_cast<const float4*>(rays), 0};
+    {
+        ProfScope ps(c, PNRT_K_PRIMARY, c->stream);
+        const unsigned gp = (unsigned)std::min<size_t>(((size_t)pb.n + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
+        if (s.has_leaf_table)
+            hipLaunchKernelGGL((pt_rays_wf<WF_STACK, true, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, c->stream, s, fp, pb, ry,
+                               c->g_primary.p);
+        else
+            hipLaunchKernelGGL((pt_rays_wf<WF_STACK, false, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, c->stream, s, fp, pb, ry,
+                               c->g_primary.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(pt_guides, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, s, (const float4*)c->g_primary,
+                       c->aov[PNRT_AOV_POSITION], c->aov[PNRT_AOV_NORMAL], c->aov[PNRT_AOV_ALBEDO], (uint32_t)pix);
+    HIPCHK(c, hipGetLastError());
+    c->guide_key = guide_key_for(c, c->cam);
+    c->guide_key.rays = true;
+    return mark_stream(c);
+}
+
+int pnrt_make_rays(pnrt_ctx* c, const pnrt_ray_camera* cam, uint32_t first, uint32_t n_sets, void* out, int64_t stride) {
+    if (!c) return PNRT_E_ARG;
+    static_assert(sizeof(pnrt_ray) == 32 && sizeof(pnrt_ray_camera) == 76, "the documented sizes");
+    if (!c->has_frame) return set_err(c, PNRT_E_STATE, "make_rays: set_frame first");
+    if (!cam) return set_err(c, PNRT_E_ARG, "make_rays: cam is NULL");
+    if (cam->model < PNRT_CAM_PINHOLE || cam->model > PNRT_CAM_FISHEYE) return set_err(c, PNRT_E_ARG, "make_rays: unknown model");
+    const float* cf = reinterpret_cast<const float*>(&cam->camera);
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(cf[i])) return set_err(c, PNRT_E_ARG, "make_rays: a camera component is not finite");
+    if (!std::isfinite(cam->fov_deg) || !std::isfinite(cam->focus_distance))
+        return set_err(c, PNRT_E_ARG, "make_rays: fov_deg or focus_distance is not finite");
+    if (cam->model == PNRT_CAM_FISHEYE && !(cam->fov_deg > 0.0f && cam->fov_deg <= 360.0f))
+        return set_err(c, PNRT_E_ARG, "make_rays: a fisheye's fov_deg must be in (0, 360]");
+    if (!(std::isfinite(cam->aa_width) && cam->aa_width >= 0.0f) || !(std::isfinite(cam->lens_radius) && cam->lens_radius >= 0.0f))
+        return set_err(c, PNRT_E_ARG, "make_rays: aa_width and lens_radius must be finite and >= 0");
+    if (cam->lens_radius > 0.0f && cam->model != PNRT_CAM_PINHOLE)
+        return set_err(c, PNRT_E_ARG, "make_rays: a lens needs PNRT_CAM_PINHOLE");
+    if (cam->lens_radius > 0.0f && !(cam->focus_distance > 0.0f))
+        return set_err(c, PNRT_E_ARG, "make_rays: a lens needs focus_distance > 0");
+    if (cam->per_pixel != 0 && cam->per_pixel != 1) return set_err(c, PNRT_E_ARG, "make_rays: per_pixel must be 0 or 1");
+    if (cam->reserved != 0) return set_err(c, PNRT_E_ARG, "make_rays: reserved must be 0");
+    if (int rc = check_frame_range(c, "make_rays", first, n_sets)) return rc;
+    if (int rc = check_ray_buffer(c, "make_rays", out, stride, n_sets)) return rc;
+    const size_t pix = (size_t)c->width * c->height;
+    if (pix > 0x7FFFFFFFull) return set_err(c, PNRT_E_ARG, "make_rays: frame too large");
+    if (n_sets == 0) return PNRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    MakeRays m;
+    cam_floats(m.eye, m.llc, m.hor, m.ver, cam->camera);
+    m.model = cam->model; m.fov_deg = cam->fov_deg;
+    m.aa_width = cam->aa_width; m.lens_radius = cam->lens_radius; m.focus_distance = cam->focus_distance;
+    m.per_pixel = cam->per_pixel;
+    m.width = c->width; m.height = c->height;
+    m.first_frame = first;
+    m.n_sets = stride == 0 ? 1u : n_sets;        // (sets 0 records apart are one set: first_frame's)
+    m.frame_stride = stride;
+    const size_t total = pix * m.n_sets;
+    if ((total + 255) / 256 > 0x7FFFFFFFull) return set_err(c, PNRT_E_ARG, "make_rays: too many records for one call");
+    {
+        ProfScope ps(c, PNRT_K_BLEND);
+        hipLaunchKernelGGL(pt_make_rays_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, m,
+                           static_cast<float4*>(out));
+    }
+    HIPCHK(c, hipGetLastError());
+    return mark_stream(c);
+}
+
 int pnrt_read_aov(pnrt_ctx* c, int which, float* out) {
     if (!c || !out) return PNRT_E_ARG;
     if (which < 0 || which >= PNRT_AOV_COUNT) return set_err(c, PNRT_E_ARG, "read_aov: unknown guide image");
@@ -2325,7 +2487,7 @@ int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_pa
         (rc = c->rp_counts.reserve(c, REPROJECT_SLOTS * sizeof(ReprojectCounts))))
         return rc;
     // the guide images of `from` (the current ones when they were rendered for it), kept as the history
-    if (!guide_key_eq(c->guide_key, guide_key_for(c, *from)))
+    if (!guide_key_eq(c->guide_key, guide_key_for(c, *from), /* camera_keyed */ true))
         if ((rc = render_guides(c, *from))) return rc;
     {
         ProfScope ps(c, PNRT_K_BLEND);

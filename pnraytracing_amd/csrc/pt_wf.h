@@ -203,13 +203,27 @@ struct WfAdapt {
 struct WfCams {
     const float* table;          // [12 * chunk_frames]
 };
-// the kernels' trailing argument pack: nothing (no list), the list, or the camera table
+// A ray batch (pnrt_render_rays, pt_rays.h) starts the path of pixel
+// (x, y) of frame slot k from the caller's ray record k * frame_stride + y * width + x: two
+// float4 (origin, -) (direction, -) at rays[2 * record].  Its camera-ray records are a camera
+// batch's: one per path slot, at primary[3 * slot].
+struct WfRays {
+    const float4* rays;          // the batch's first set
+    int64_t frame_stride;        // records between the sets of consecutive frames (0: one set)
+};
+// the kernels' trailing argument pack: nothing (no list), the list, the camera table or the rays
 PN_DEV WfAdapt wf_adapt() { return WfAdapt{nullptr, 0u}; }
 PN_DEV WfAdapt wf_adapt(const WfAdapt& ad) { return ad; }
 PN_DEV WfAdapt wf_adapt(const WfCams&) { return WfAdapt{nullptr, 0u}; }
+PN_DEV WfAdapt wf_adapt(const WfRays&) { return WfAdapt{nullptr, 0u}; }
 PN_DEV WfCams wf_cams() { return WfCams{nullptr}; }
 PN_DEV WfCams wf_cams(const WfAdapt&) { return WfCams{nullptr}; }
 PN_DEV WfCams wf_cams(const WfCams& cm) { return cm; }
+PN_DEV WfCams wf_cams(const WfRays&) { return WfCams{nullptr}; }
+PN_DEV WfRays wf_rays() { return WfRays{nullptr, 0}; }
+PN_DEV WfRays wf_rays(const WfAdapt&) { return WfRays{nullptr, 0}; }
+PN_DEV WfRays wf_rays(const WfCams&) { return WfRays{nullptr, 0}; }
+PN_DEV WfRays wf_rays(const WfRays& ry) { return ry; }
 template <class T, class... AD>
 inline constexpr bool wf_pack_is = (std::is_same_v<T, AD> || ...);
 // -> whether the slot's pixel is active (a lane of an inactive pixel starts no path)
@@ -280,10 +294,10 @@ PN_DEV void wf_put_color(const WfBufs& b, const FrameParams& fp, float4* colors,
 PN_DEV const float4* wf_primary(const WfBufs& b, const FrameParams& fp, const float4* primary, int lr, int x) {
     return primary + 3 * PT_CHECK(b.fault, (size_t)lr * fp.width + x, (size_t)fp.rows * fp.width, PT_SITE_PRIMARY);
 }
-// ... of a camera batch: the record of the path's own camera ray, at its slot
-template <bool CAMS>
+// ... of a camera or ray batch (PER_SLOT): the record of the path's own camera ray, at its slot
+template <bool PER_SLOT>
 PN_DEV const float4* wf_primary_of(const WfBufs& b, const FrameParams& fp, const float4* primary, uint32_t slot, int lr, int x) {
-    if constexpr (CAMS) return primary + 3 * PT_CHECK(b.fault, (size_t)slot, (size_t)b.n, PT_SITE_PRIMARY);
+    if constexpr (PER_SLOT) return primary + 3 * PT_CHECK(b.fault, (size_t)slot, (size_t)b.n, PT_SITE_PRIMARY);
     else return wf_primary(b, fp, primary, lr, x);
 }
 // CameraGetRay (camera_dir, pt_passes.h: the same operations in the same order) for
@@ -298,6 +312,13 @@ PN_DEV f3 wf_camera_dir(const FrameParams& fp, const WfCams& cm, int k, int px, 
     eye = mk3(t[0], t[1], t[2]);
     float sx = (float)px / (float)fp.width, sy = (float)py / (float)fp.height;
     return normalize(sub(add(add(mk3(t[3], t[4], t[5]), smul(sx, mk3(t[6], t[7], t[8]))), smul(sy, mk3(t[9], t[10], t[11]))), eye));
+}
+
+// The caller's ray record of pixel (px, py) of frame slot k of a ray batch: its two float4.
+PN_DEV const float4* wf_ray_record(const WfBufs& b, const FrameParams& fp, const WfRays& ry, int k, int px, int py) {
+    const size_t set = (size_t)fp.width * fp.height;
+    const size_t at = (size_t)k * (size_t)ry.frame_stride + (size_t)py * fp.width + px;
+    return ry.rays + 2 * PT_CHECK(b.fault, at, (size_t)(b.chunk_frames - 1) * (size_t)ry.frame_stride + set, PT_SITE_RAY);
 }
 
 // Path state a bounce's setup starts from (in registers: the fused kernels
@@ -697,14 +718,16 @@ PN_DEV void wf_enqueue(const WfBufs& b, uint32_t i, uint32_t nfl, const BounceRa
 
 // ---- gen + bounce-0 setup: start every path from its pixel's primary hit -------------------
 // AD: empty (pt_wf_gen_setup<>, the slots of a pnrt_render batch: the kernel's five
-// arguments), WfAdapt (the slots of an adaptive batch, through its list) or WfCams (a
-// camera batch: `primary` holds a record per slot, V comes from the frame's camera).
+// arguments), WfAdapt (the slots of an adaptive batch, through its list), WfCams (a
+// camera batch: `primary` holds a record per slot, V comes from the frame's camera) or
+// WfRays (a ray batch: a record per slot, V comes from the caller's ray).
 template <class... AD>
 __global__ void __launch_bounds__(256, WF_GEN_WAVES) pt_wf_gen_setup(DevScene s, FrameParams fp, WfBufs b, const float4* primary,
                                                        float4* colors, AD... adv) {
-    constexpr bool ADAPT = wf_pack_is<WfAdapt, AD...>, CAMS = wf_pack_is<WfCams, AD...>;
+    constexpr bool ADAPT = wf_pack_is<WfAdapt, AD...>, CAMS = wf_pack_is<WfCams, AD...>, RAYS = wf_pack_is<WfRays, AD...>;
     const WfAdapt ad = wf_adapt(adv...);
     [[maybe_unused]] const WfCams cm = wf_cams(adv...);
+    [[maybe_unused]] const WfRays ry = wf_rays(adv...);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;     // path slot
     wf_reset_counters(b);
     wf_live_init();
@@ -728,7 +751,7 @@ __global__ void __launch_bounds__(256, WF_GEN_WAVES) pt_wf_gen_setup(DevScene s,
         if constexpr (ADAPT) active = wf_coords_adaptive(b, ad, i, x, lr, k);    // (a clear mask bit: no path, no colour)
         else wf_coords(b, i, x, lr, k);
         if (active && x < fp.width && lr < fp.rows) {
-            const float4* rec = wf_primary_of<CAMS>(b, fp, primary, i, lr, x);
+            const float4* rec = wf_primary_of<CAMS || RAYS>(b, fp, primary, i, lr, x);
             const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2];
             const int mt = __float_as_int(q0.w);
             const f3 base = mk3(q2.y, q2.z, q2.w);
@@ -742,6 +765,7 @@ __global__ void __launch_bounds__(256, WF_GEN_WAVES) pt_wf_gen_setup(DevScene s,
                 q.P = mk3(q0.x, q0.y, q0.z); q.N = mk3(q1.x, q1.y, q1.z);
                 q.u = q1.w; q.v = q2.x; q.mt = mt;
                 if constexpr (CAMS) { f3 eye; q.V = neg(wf_camera_dir(fp, cm, k, x, py, eye)); }
+                else if constexpr (RAYS) { const float4 d = wf_ray_record(b, fp, ry, k, x, py)[1]; q.V = neg(mk3(d.x, d.y, d.z)); }
                 else q.V = neg(camera_dir(fp, x, py));
                 q.cw = mk3(1.f, 1.f, 1.f);
                 q.Lo = mk3(0.f, 0.f, 0.f);
@@ -1956,7 +1980,7 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, PT_PRIM_WF_WAVES) pt_primary_w
 // ---- shade: MIS, continuation hit, next bounce or final colour (:936-972) --------------------
 // Path entry i of the read set.  Returns whether the path continues; then q,
 // bounce, slot and the pixel / frame carry its next bounce to the setup.
-template <bool ADAPT, bool CAMS = false>
+template <bool ADAPT, bool PER_SLOT = false>
 PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs& b, const WfAdapt& ad, const float4* primary,
                           float4* colors, uint32_t i, PathIn& q, int& bounce, uint32_t& slot, int& x, int& py,
                           uint32_t& frame) {
@@ -2002,7 +2026,7 @@ PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs
             f3 enLi = env_color(s, normalize(L));
             Lo = add(Lo, divs(muls(mul(mul(cw, enLi), dBRDF), NdotL), dPDF));
         }
-        const float4 q2 = wf_primary_of<CAMS>(b, fp, primary, slot, lr, x)[2];     // the primary hit's base colour
+        const float4 q2 = wf_primary_of<PER_SLOT>(b, fp, primary, slot, lr, x)[2];     // the primary hit's base colour
         wf_put_color<ADAPT>(b, fp, colors, slot, k, lr, x, add(mk3(q2.y, q2.z, q2.w), Lo));
         return false;
     }
@@ -2013,7 +2037,7 @@ PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs
     cw = mul(cw, divs(muls(dBRDF, NdotL), dPDF));
     ++bounce;
     if (bounce >= fp.max_depth) {
-        const float4 q2 = wf_primary_of<CAMS>(b, fp, primary, slot, lr, x)[2];
+        const float4 q2 = wf_primary_of<PER_SLOT>(b, fp, primary, slot, lr, x)[2];
         wf_put_color<ADAPT>(b, fp, colors, slot, k, lr, x, add(mk3(q2.y, q2.z, q2.w), Lo));
         return false;
     }
@@ -2033,7 +2057,8 @@ PN_DEV bool wf_shade_path(const DevScene& s, const FrameParams& fp, const WfBufs
 template <bool FINAL, class... AD>
 __global__ void __launch_bounds__(256, FINAL ? 8 : WF_SHADE_WAVES) pt_wf_shade_setup(DevScene s, FrameParams fp, WfBufs b,
                                                                      const float4* primary, float4* colors, AD... adv) {
-    constexpr bool ADAPT = wf_pack_is<WfAdapt, AD...>, CAMS = wf_pack_is<WfCams, AD...>;
+    // (a ray batch's records sit where a camera batch's do: per slot)
+    constexpr bool ADAPT = wf_pack_is<WfAdapt, AD...>, PER_SLOT = wf_pack_is<WfCams, AD...> || wf_pack_is<WfRays, AD...>;
     const WfAdapt ad = wf_adapt(adv...);
     [[maybe_unused]] const WfCams cm = wf_cams(adv...);
     // the block's live paths are its first b.rd.bcount[block] entries
@@ -2051,7 +2076,7 @@ __global__ void __launch_bounds__(256, FINAL ? 8 : WF_SHADE_WAVES) pt_wf_shade_s
     PathIn q;
     int bounce = 0, x = 0, py = 0;
     uint32_t slot = 0, frame = 0;
-    if (threadIdx.x < live) cont = wf_shade_path<ADAPT, CAMS>(s, fp, b, ad, primary, colors, i, q, bounce, slot, x, py, frame);
+    if (threadIdx.x < live) cont = wf_shade_path<ADAPT, PER_SLOT>(s, fp, b, ad, primary, colors, i, q, bounce, slot, x, py, frame);
     if (FINAL) return;                        // bounce + 1 == max_depth: cont is false for every path
     const uint32_t j = blockIdx.x * 256u + wf_entry_rank(cont);
     uint32_t nfl = 0;

@@ -102,6 +102,10 @@ class ShardedFrame:
         """``render`` with a camera per frame (``PathTracer.render_cameras``) over this rank's rows."""
         self.tracer.render_cameras(first_frame, cameras, self.band, self.world, self.rank)
 
+    def render_rays(self, first_frame: int, n_frames: int, rays, frame_stride: int = 0):
+        """``render`` from caller rays (``PathTracer.render_rays``; the buffer covers the whole image) over this rank's rows."""
+        self.tracer.render_rays(first_frame, n_frames, rays, frame_stride, self.band, self.world, self.rank)
+
     def _gather(self) -> torch.Tensor | None:
         """Pack this rank's rows, gather on rank 0; returns the H x W x 4 image
         (row 0 = bottom) on rank 0 and None elsewhere."""

@@ -77,6 +77,8 @@ class CameraController:
 class InteractiveSession:
     """main.cpp:573-630 without the window: one ``frame()`` per loop iteration."""
 
+    _model = _guide_rays = _guide_view = None        # (class defaults: no camera model, guides keyed by the camera)
+
     def __init__(self, tracer, width: int, height: int, camera: CameraController, max_bounce_depth: int = 4):
         self.pt = tracer
         self.width, self.height = width, height
@@ -85,6 +87,10 @@ class InteractiveSession:
         self.frame_count = 0
         self._rendered_camera = None                 # uniforms of the last call that rendered (reproject's `from`)
         self._lens = None                            # set_lens: (aa_width, lens_radius, focus_distance)
+        self._model = None                           # set_camera_model: (model, fov_deg, per_pixel)
+        self._rays = None                            # the ray buffer of the last frame (alive while its call runs)
+        self._guide_rays = None                      # the ray buffer of the guide images, and what it was made for:
+        self._guide_view = None                      # (camera uniforms, model, fov_deg, size); None: camera-keyed guides
 
     def set_lens(self, aa_width: float = 1.0, lens_radius: float = 0.0, focus_distance: float | None = None):
         """Anti-aliasing and depth of field for the still frames: from now on ``frame()``
@@ -97,7 +103,40 @@ class InteractiveSession:
             focus_distance = self._lens[2] if self._lens else None
             if focus_distance is None:
                 raise ValueError("set_lens: a lens needs a focus_distance (or focus_on(px, py) first)")
+        if lens_radius > 0 and self._model is not None and self._model[0] != "pinhole":
+            raise ValueError(f"set_lens: a lens needs the pinhole model (set_camera_model: {self._model[0]!r})")
         self._lens = (float(aa_width), float(lens_radius), None if focus_distance is None else float(focus_distance))
+
+    def set_camera_model(self, model, fov_deg: float = 180.0, per_pixel: bool = False):
+        """Another camera model for the still frames: from now on ``frame()`` and
+        ``frame_counted()`` make the rays of frame ``frame_count`` on the device
+        (``PathTracer.make_rays``: ``"pinhole"``, ``"ortho"``, ``"equirect"`` or ``"fisheye"``
+        over the controller's uniforms, with ``set_lens``'s pixel filter and -- pinhole only --
+        lens, sampled per frame or, with ``per_pixel``, per pixel) and render them with
+        ``PathTracer.render_rays``; ``preview()`` takes its guide images from the model's
+        un-jittered rays (the pinhole model keeps ``render_guides``), made again whenever the
+        camera, the model or ``fov_deg`` has changed since; ``reproject()`` is refused under
+        another model than pinhole.  A redraw stays the reference's depth-1 frame 0 of the pinhole camera when the
+        model is pinhole, and is the same frame through the ray path otherwise.  Never
+        called, nothing changes."""
+        from . import _native as N_
+        if isinstance(model, str) and model not in N_.CAM_MODELS:
+            raise ValueError(f"unknown camera model {model!r}: one of {N_.CAM_MODELS}")
+        name = model if isinstance(model, str) else N_.CAM_MODELS[int(model)]
+        if name != "pinhole" and self._lens is not None and self._lens[1] > 0:
+            raise ValueError("set_camera_model: a lens (set_lens) needs the pinhole model")
+        self._model = (name, float(fov_deg), int(bool(per_pixel)))
+
+    def _model_rays(self, cam, n: int, jitter: bool = True):
+        """(rays, frame_stride) of frames frame_count .. + n - 1 for the camera model."""
+        name, fov, per_pixel = self._model
+        aa, radius, focus = self._lens if (self._lens is not None and jitter) else (0.0, 0.0, None)
+        lens = radius > 0 and focus is not None
+        still = not (aa > 0 or lens)                 # no sample: one set serves every frame
+        self._rays = self.pt.make_rays(name, cam, self.frame_count, 1 if still else n, fov_deg=fov, aa_width=aa,
+                                       lens_radius=radius if lens else 0.0, focus_distance=focus if lens else 0.0,
+                                       per_pixel=per_pixel)
+        return self._rays, 0 if (still or n == 1) else self.width * self.height
 
     def focus_on(self, px: int, py: int) -> bool:
         """Focus on what is under pixel (px, py): ``focus_distance`` becomes the distance of
@@ -130,7 +169,10 @@ class InteractiveSession:
             depth = self.max_bounce_depth
         cam = self.camera.uniforms()
         self.pt.set_frame(self.width, self.height, cam, depth)
-        if self._lens is not None and not redraw:
+        if self._model is not None and not (redraw and self._model[0] == "pinhole"):
+            rays, stride = self._model_rays(cam, 1, jitter=not redraw)
+            self.pt.render_rays(self.frame_count, 1, rays, stride, band, n_shards, shard)
+        elif self._lens is not None and not redraw:
             self.pt.render_cameras(self.frame_count, self._lens_cameras(cam, 1), band, n_shards, shard)
         else:
             self.pt.render(self.frame_count, 1, band, n_shards, shard)   # main.cpp:612-613
@@ -192,11 +234,14 @@ class InteractiveSession:
         with ``frame_counted()``.  Needs the sample moments enabled since the
         accumulation was last reset (``frame_counted``, ``render_until`` and
         ``render_adaptive_until`` enable them).  Returns the call's statistics."""
+        if self._model is not None and self._model[0] != "pinhole":
+            raise ValueError(f"reproject: the {self._model[0]!r} camera model has no reprojection (pinhole views only)")
         if self.frame_count == 0 or self._rendered_camera is None:
             raise ValueError("reproject: nothing was rendered yet (frame_count == 0)")
         cam = self.camera.uniforms()
         self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
         stats = self.pt.reproject(self._rendered_camera, **params)
+        self._guide_view = None                      # it left camera-keyed guides of the new view
         self._rendered_camera = cam
         return stats
 
@@ -211,8 +256,12 @@ class InteractiveSession:
         self.pt.enable_moments(True)
         cam = self.camera.uniforms()
         self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
-        if self._lens is not None:
-            self.pt.render_cameras(self.frame_count, self._lens_cameras(cam, n))
+        if self._model is not None or self._lens is not None:
+            if self._model is not None:
+                rays, stride = self._model_rays(cam, n)
+                self.pt.render_rays(self.frame_count, n, rays, stride)
+            else:
+                self.pt.render_cameras(self.frame_count, self._lens_cameras(cam, n))
             plan = self.pt.cameras_batch_plan(n)
             npix, ntiles = self.width * self.height, ((self.width + 7) // 8) * ((self.height + 7) // 8)
             self._rendered_camera = cam
@@ -246,19 +295,49 @@ class InteractiveSession:
         ray = camera_pixel_ray(self.camera.uniforms(), px, py, self.width, self.height)
         return {k: v[0] for k, v in decode_hits(self.pt.query_rays(ray)).items()}
 
+    def _guide_want(self):
+        """What ray-made guide images must have been made for to show the view the still frames render; None
+        when that view is the camera's own (no model, or pinhole): camera-keyed guides, whose staleness the
+        library judges itself."""
+        if self._model is None or self._model[0] == "pinhole":
+            return None
+        name, fov, _ = self._model
+        return (self.camera.uniforms().tobytes(), name, fov, self.width, self.height)
+
+    def _render_guides(self):
+        """The guide images of the view the still frames render: the camera's, or the camera model's centre rays."""
+        want = self._guide_want()
+        if want is None:
+            self._guide_rays = None
+            self.pt.render_guides()
+        else:
+            _, name, fov, _, _ = want
+            self._guide_rays = self.pt.make_rays(name, self.camera.uniforms(), 0, 1, fov_deg=fov)
+            self.pt.render_guides_rays(self._guide_rays)
+        self._guide_view = want
+
+    def _guides_for_this_view(self):
+        """Guide images made from rays carry no camera, so the library cannot tell that they belong to another
+        view: the session remembers what it made them for and renders them again when that has changed."""
+        if self._guide_want() != self._guide_view:
+            self._render_guides()
+
     def preview(self, **params):
         """The denoised preview of the accumulation image as it stands (after ``frame()``,
         before the display: main.cpp:613 / :618-628).  The guide images are rendered only
         when the camera or the scene changed since the last call -- the library says so
-        (PNRT_E_STATE from pnrt_denoise) -- then the image is filtered.  ``params`` are
+        (PNRT_E_STATE from pnrt_denoise); under another camera model than pinhole the guides
+        are made from rays and carry no camera, so there the session itself compares the
+        view they were made for -- then the image is filtered.  ``params`` are
         ``PathTracer.denoise``'s; read the result with ``PathTracer.read_denoised()``."""
         from .tracer import PnrtError
+        self._guides_for_this_view()
         try:
             self.pt.denoise(**params)
         except PnrtError as e:
             if getattr(e, "code", 0) != -3:          # PNRT_E_STATE: no guides yet, or stale ones
                 raise
-            self.pt.render_guides()
+            self._render_guides()
             self.pt.denoise(**params)
 
     def show(self, denoised: bool = False, auto_exposure: bool = False, **display_params) -> np.ndarray:
@@ -285,10 +364,11 @@ class InteractiveSession:
         about the moments (never enabled, or not covering the accumulation) is raised
         with its message."""
         from .tracer import PnrtError
+        self._guides_for_this_view()
         try:
             self.pt.denoise_variance(**params)
         except PnrtError as e:
             if getattr(e, "code", 0) != -3 or "render_guides" not in str(e):
                 raise
-            self.pt.render_guides()
+            self._render_guides()
             self.pt.denoise_variance(**params)

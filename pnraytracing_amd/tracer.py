@@ -44,6 +44,8 @@ class PathTracer:
         if rc != 0:
             raise PnrtError(f"pnrt_create(device={device}) failed ({rc}): no usable HIP device")
         self._ctx = ctx
+        self._device = device
+        self._stream = 0                 # set_stream's handle (0: the context's own stream)
         self.width = self.height = 0
 
     def close(self):
@@ -174,6 +176,11 @@ class PathTracer:
 
     def set_stream(self, stream_handle: int | None):
         self._ck(self._lib.pnrt_set_stream(self._ctx, ctypes.c_void_p(stream_handle or 0)), "pnrt_set_stream")
+        self._stream = stream_handle or 0
+
+    def current_stream_handle(self) -> int:
+        """The hipStream_t the context queues on now: ``set_stream``'s, or its own."""
+        return self._stream or self.stream_handle()
 
     def load(self, cfg, traverse_mode: int = TRAVERSE_ZCULL):
         """Upload a :class:`pnraytracing_amd.scenes.SceneConfig`."""
@@ -228,6 +235,85 @@ class PathTracer:
         self._ck(self._lib.pnrt_cameras_batch_plan(self._ctx, n_frames, band, n_shards, shard, ctypes.byref(fpb),
                                                    ctypes.byref(nb), ctypes.byref(by)), "pnrt_cameras_batch_plan")
         return {"frames_per_batch": fpb.value, "n_batches": nb.value, "batch_bytes": by.value}
+
+    # ---- caller ray buffers ---------------------------------------------------------------
+    @staticmethod
+    def _rays_ptr(rays) -> int:
+        """A device ray buffer as an address: a torch tensor on the device (its data pointer) or an integer."""
+        if isinstance(rays, int):
+            return rays
+        if hasattr(rays, "data_ptr") and hasattr(rays, "is_cuda"):
+            if not rays.is_cuda:
+                raise ValueError("rays must be a tensor on the device (or an integer device pointer)")
+            if not rays.is_contiguous():
+                raise ValueError("rays must be contiguous")
+            return int(rays.data_ptr())
+        raise ValueError("rays must be a torch tensor on the device or an integer device pointer")
+
+    def render_rays(self, first_frame: int, n_frames: int, rays, frame_stride: int = 0, band: int = 1, n_shards: int = 1,
+                    shard: int = 0):
+        """``render`` from caller rays (pnrt_render_rays): pixel (x, y) of frame ``first_frame + k``
+        starts from record ``k * frame_stride + y * width + x`` of ``rays`` -- a torch tensor on
+        the device or an integer device pointer, 16-byte aligned, 8 floats per record (origin,
+        -, direction, -), one record per pixel of the whole image.  ``frame_stride`` 0: one set
+        serves every frame.  A record with a non-finite float or a zero direction is no ray:
+        frame colour 0.  Asynchronous; the buffer is not copied -- keep it unchanged (and
+        alive) until the work has completed."""
+        for name, v in (("first_frame", first_frame), ("n_frames", n_frames)):
+            if not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError(f"render_rays: {name} = {v} is outside 0 .. 2**32 - 1")
+        if not -2 ** 63 <= frame_stride < 2 ** 63:
+            raise ValueError(f"render_rays: frame_stride = {frame_stride} does not fit 64 bits")
+        ptr = 0 if rays is None else self._rays_ptr(rays)
+        self._ck(self._lib.pnrt_render_rays(self._ctx, first_frame, n_frames, ctypes.c_void_p(ptr), frame_stride, band, n_shards,
+                                            shard), "pnrt_render_rays")
+
+    def render_guides_rays(self, rays):
+        """``render_guides`` with the camera rays of one set of ``width * height`` records
+        (pnrt_render_guides_rays); asynchronous.  The guides carry no camera: ``denoise``,
+        ``denoise_variance`` and ``read_aov`` accept them until the frame size, the scene or
+        the traversal mode changes or ``render_guides`` / ``reproject`` replaces them."""
+        ptr = 0 if rays is None else self._rays_ptr(rays)
+        self._ck(self._lib.pnrt_render_guides_rays(self._ctx, ctypes.c_void_p(ptr)), "pnrt_render_guides_rays")
+
+    @staticmethod
+    def ray_camera(model, camera, fov_deg: float = 180.0, aa_width: float = 0.0, lens_radius: float = 0.0,
+                   focus_distance: float = 0.0, per_pixel: int = 0, reserved: int = 0) -> "N.RayCamera":
+        """A ``pnrt_ray_camera``: ``model`` a name of ``CAM_MODELS`` or its number, ``camera`` the (4, 3) uniforms."""
+        rc = N.RayCamera()
+        rc.model = PathTracer._enum("camera model", N.CAM_MODELS, model)
+        c = np.asarray(camera, np.float32).reshape(4, 3)
+        rc.camera.eye[:], rc.camera.lower_left[:], rc.camera.horizontal[:], rc.camera.vertical[:] = (list(map(float, r)) for r in c)
+        rc.fov_deg, rc.aa_width, rc.lens_radius, rc.focus_distance = fov_deg, aa_width, lens_radius, focus_distance
+        rc.per_pixel, rc.reserved = int(per_pixel), int(reserved)
+        return rc
+
+    def make_rays(self, model, camera, first_frame: int = 0, n_sets: int = 1, frame_stride: int | None = None, out=None,
+                  **params):
+        """Ray sets of a camera model made on the device (pnrt_make_rays; asynchronous on the
+        context's stream): ``n_sets`` sets for frames ``first_frame ..`` at the current frame
+        size, ``frame_stride`` records apart (None: ``width * height``, or 0 for one set).
+        ``params`` are ``ray_camera``'s (fov_deg, aa_width, lens_radius, focus_distance,
+        per_pixel).  Returns the buffer: ``out`` when given (a float32 tensor on the device,
+        or an integer pointer), else a new float32 tensor of shape (records, 8) -- allocated
+        and filled on the wrapped context stream."""
+        for name, v in (("first_frame", first_frame), ("n_sets", n_sets)):
+            if not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError(f"make_rays: {name} = {v} is outside 0 .. 2**32 - 1")
+        pix = self.width * self.height
+        if frame_stride is None:
+            frame_stride = pix if n_sets > 1 else 0
+        rc = self.ray_camera(model, camera, **params)
+        if out is None:
+            import torch
+            records = pix if (frame_stride == 0 or n_sets == 0) else (n_sets - 1) * frame_stride + pix
+            dev = torch.device("cuda", self._device)
+            with torch.cuda.stream(torch.cuda.ExternalStream(self.current_stream_handle(), device=dev)):
+                out = torch.empty((max(records, 1), 8), dtype=torch.float32, device=dev)
+        ptr = self._rays_ptr(out)
+        self._ck(self._lib.pnrt_make_rays(self._ctx, ctypes.byref(rc), first_frame, n_sets, ctypes.c_void_p(ptr), frame_stride),
+                 "pnrt_make_rays")
+        return out
 
     def reset_accum(self):
         self._ck(self._lib.pnrt_reset_accum(self._ctx), "pnrt_reset_accum")
