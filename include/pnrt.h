@@ -266,9 +266,10 @@ int pnrt_batch_plan(pnrt_ctx* ctx, uint32_t n_frames, int band_rows, int n_shard
  * or any of the 12 * n_frames floats not finite (the message names the frame);
  * PNRT_E_TRACE as pnrt_render.  n_frames == 0 or a shard without rows: PNRT_OK,
  * nothing queued.
- * Out of scope: an adaptive variant (pnrt_render_adaptive renders the
- * pnrt_set_frame camera), a device-array form of `cameras`, and per-pixel (rather
- * than per-frame) lens samples. */
+ * Out of scope: an adaptive variant over `cameras` (adaptive sampling goes through
+ * rays: pnrt_make_rays makes these cameras' rays, pnrt_render_rays_adaptive renders
+ * them), a device-array form of `cameras`, and per-pixel (rather than per-frame)
+ * lens samples. */
 int pnrt_render_cameras(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames, const pnrt_camera* cameras,
                         int band_rows, int n_shards, int shard);
 /* pnrt_batch_plan for a pnrt_render_cameras call: the same rules over the larger
@@ -313,8 +314,9 @@ int pnrt_cameras_batch_plan(pnrt_ctx* ctx, uint32_t n_frames, int band_rows, int
  * passes 2^63 bytes, a bad selector,
  * first_frame + n_frames > 0xFFFFFFFF; PNRT_E_TRACE as pnrt_render.  n_frames == 0 or a
  * shard without rows: PNRT_OK, nothing queued.
- * Out of scope: an adaptive variant, pnrt_reproject across ray sets, a host-array form,
- * a tMax or near clip per ray. */
+ * The adaptive variant is pnrt_render_rays_adaptive.
+ * Out of scope: pnrt_reproject across ray sets, a host-array form, a tMax or near clip
+ * per ray. */
 typedef struct { float origin[3], reserved0, direction[3], reserved1; } pnrt_ray;   /* 32 bytes */
 int pnrt_render_rays(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames, const void* rays_dev, int64_t frame_stride,
                      int band_rows, int n_shards, int shard);
@@ -613,6 +615,25 @@ int pnrt_render_adaptive(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames,
                          float threshold, uint32_t min_frames,
                          int band_rows, int n_shards, int shard,
                          pnrt_adaptive_stats* out /* may be NULL */);
+/* pnrt_render_adaptive over caller ray buffers: the conjunction of that call and
+ * pnrt_render_rays.  The mask, the tiles, the waiting, the fold
+ * of an active pixel's frames, the untouched inactive pixel, the moments-state and
+ * PNRT_KERNEL_V1 refusals, n_frames == 0 and `out` are pnrt_render_adaptive's; the
+ * colour of an active pixel is the one pnrt_render_rays would produce for that pixel,
+ * frame and ray record, bit for bit (a "no ray" record: (0, 0, 0), folded like any
+ * other), and the buffer, its rules, its read ordering, which set a batch's frame slot
+ * reads, and what the call leaves alone (the pnrt_set_frame camera, the kept per-pixel
+ * camera-ray records, the guide images) are pnrt_render_rays'.  The values of inactive
+ * pixels' records do not matter: no result depends on them.  The batch plan runs on
+ * 64 * n_active_tiles path slots per frame with pnrt_render_rays' 48 more bytes per
+ * path, which PNRT_BATCH_BYTES caps; the ray launch is PNRT_K_PRIMARY, one per batch,
+ * the other classes are pnrt_render_adaptive's.  PNRT_E_ARG, with nothing queued and
+ * nothing changed: either call's argument errors. */
+int pnrt_render_rays_adaptive(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames,
+                              const void* rays_dev, int64_t frame_stride,
+                              float threshold, uint32_t min_frames,
+                              int band_rows, int n_shards, int shard,
+                              pnrt_adaptive_stats* out /* may be NULL */);
 
 /* Temporal reprojection (not in the reference, whose redraw starts the image again from
  * one sample: main.cpp:592-596): after a camera move, resample the accumulation and the

@@ -278,6 +278,8 @@ def _type_device(lib):
     _sig(lib, "pnrt_cameras_batch_plan", INT, P, ctypes.c_uint32, INT, INT, INT, ctypes.POINTER(ctypes.c_uint32),
          ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int64))
     _sig(lib, "pnrt_render_rays", INT, P, ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_int64, INT, INT, INT)
+    _sig(lib, "pnrt_render_rays_adaptive", INT, P, ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_int64, ctypes.c_float,
+         ctypes.c_uint32, INT, INT, INT, ctypes.POINTER(AdaptiveStats))
     _sig(lib, "pnrt_render_guides_rays", INT, P, P)
     _sig(lib, "pnrt_make_rays", INT, P, ctypes.POINTER(RayCamera), ctypes.c_uint32, ctypes.c_uint32, P, ctypes.c_int64)
 

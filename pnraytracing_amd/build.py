@@ -138,6 +138,8 @@ ABI_CALLERS = {
     "c_abi_cameras.c": ["-lpnrt_host", "-lm"],
     # a fisheye ray set (pnrt_make_rays) rendered with pnrt_render_rays and pnrt_render_guides_rays (tests/test_gpu_rays_c_abi.py)
     "c_abi_rays.c": ["-lamdhip64"],
+    # pnrt_render_rays(0, 4), then pnrt_render_rays_adaptive over fisheye sets (tests/test_gpu_rays_adaptive_c_abi.py)
+    "c_abi_rays_adaptive.c": ["-lamdhip64"],
 }
 
 
@@ -164,13 +166,13 @@ def _abi_caller(source, force):
 
 
 def build_abi_caller(force=False):
-    """tests/abi/c_abi_render and the callers that came with it (every ABI_CALLERS entry but the two below);
+    """tests/abi/c_abi_render and the callers that came with it (every ABI_CALLERS entry but those below);
     None, and nothing built, without c_abi_render's source, both headers and both libraries."""
     need = [os.path.join(REPO, "tests", "abi", "c_abi_render.cpp"), os.path.join(INC, "pnrt.h"), os.path.join(INC, "pnrt_host.h"),
             os.path.join(PKG, "libpnrt.so"), os.path.join(PKG, "libpnrt_host.so")]
     if not all(os.path.exists(d) for d in need):
         return None
-    outs = [_abi_caller(source, force) for source in ABI_CALLERS if source not in ("c_abi_refit.c", "c_abi_cameras.c", "c_abi_rays.c")]
+    outs = [_abi_caller(source, force) for source in ABI_CALLERS if source not in ("c_abi_refit.c", "c_abi_cameras.c", "c_abi_rays.c", "c_abi_rays_adaptive.c")]
     return outs[0]
 
 
@@ -184,6 +186,10 @@ def build_cameras_abi_caller(force=False):
 
 def build_rays_abi_caller(force=False):
     return _abi_caller("c_abi_rays.c", force)
+
+
+def build_rays_adaptive_abi_caller(force=False):
+    return _abi_caller("c_abi_rays_adaptive.c", force)
 
 
 def build_oracle(force=False):
@@ -202,6 +208,7 @@ def build_all(force=False):
     build_refit_abi_caller(force)
     build_cameras_abi_caller(force)
     build_rays_abi_caller(force)
+    build_rays_adaptive_abi_caller(force)
     build_oracle(force)
 
 

@@ -571,7 +571,7 @@ static int report_trace_diag(pnrt_ctx* c, const WfBufs& b, hipStream_t st, int b
 // its colours land in frame slots [0, cf) of `colors`.
 static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const WfLayout& L, hipStream_t st,
                         const float4* primary, float4* colors, bool alone, bool one, hipEvent_t stage = nullptr,
-                        const WfAdapt* ad = nullptr,       // ad: an adaptive batch's slots (pt_adaptive.h)
+                        const WfAdapt* ad = nullptr,       // ad: an adaptive batch's slots (pt_adaptive.h); with ry: over its rays
                         const WfCams* cm = nullptr,        // cm: a camera batch's table (pt_cameras.h; primary = its records)
                         const WfRays* ry = nullptr) {      // ry: a ray batch's rays (pt_rays.h; primary = its records)
     WfBufs b = L.b;
@@ -588,7 +588,8 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
     if (WF_STATS) HIPCHK(c, hipMemsetAsync(b.stats + 56, 0, 64, st));    // the setups' moot-ray counts
     {   // path state + bounce-0 sampling
         ProfScope ps(c, PNRT_K_GEN, st);
-        if (ad) hipLaunchKernelGGL(pt_wf_gen_setup<WfAdapt>, g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
+        if (ad && ry) hipLaunchKernelGGL((pt_wf_gen_setup<WfAdapt, WfRays>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad, *ry);
+        else if (ad) hipLaunchKernelGGL(pt_wf_gen_setup<WfAdapt>, g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
         else if (cm) hipLaunchKernelGGL(pt_wf_gen_setup<WfCams>, g, dim3(256), 0, st, s, fp, b, primary, colors, *cm);
         else if (ry) hipLaunchKernelGGL(pt_wf_gen_setup<WfRays>, g, dim3(256), 0, st, s, fp, b, primary, colors, *ry);
         else hipLaunchKernelGGL(pt_wf_gen_setup<>, g, dim3(256), 0, st, s, fp, b, primary, colors);
@@ -626,7 +627,11 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
             // the trace launch that follows it (gen has no test: whole ranges, no lists)
             b.lidx = L.lidx;
             b.cidx = bounce + 2 == fp.max_depth ? L.cidx : nullptr;
-            if (ad && fin)
+            if (ad && ry && fin)
+                hipLaunchKernelGGL((pt_wf_shade_setup<true, WfAdapt, WfRays>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad, *ry);
+            else if (ad && ry)
+                hipLaunchKernelGGL((pt_wf_shade_setup<false, WfAdapt, WfRays>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad, *ry);
+            else if (ad && fin)
                 hipLaunchKernelGGL((pt_wf_shade_setup<true, WfAdapt>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
             else if (ad)
                 hipLaunchKernelGGL((pt_wf_shade_setup<false, WfAdapt>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
@@ -835,7 +840,7 @@ struct BatchRoute {
     int ovf_stride, tiles_x;
     const WfAdapt* ad;       // an adaptive call's active-tile list, or null
     const float* cams;       // pnrt_render_cameras: the call's cameras (pinned host memory, 12 floats per frame), or null
-    const float4* rays;      // pnrt_render_rays: the call's first set (device memory), or null,
+    const float4* rays;      // pnrt_render_rays, pnrt_render_rays_adaptive (with ad): the call's first set (device memory), or null,
     int64_t ray_stride;      // and the records between the sets of consecutive frames
 };
 // The batches of one call on pipe P: per group of `chunk` frames one batch (gen ->
@@ -882,7 +887,13 @@ static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pn
             primary = P.camrec;
             ProfScope ps(c, PNRT_K_PRIMARY, w);
             const unsigned gp = (unsigned)std::min<size_t>(((size_t)a.b.n + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
-            if (s.has_leaf_table)
+            if (R.ad && s.has_leaf_table)     // (an adaptive call's: the list's slots)
+                hipLaunchKernelGGL((pt_rays_wf<WF_STACK, true, false, WfAdapt>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, ry,
+                                   P.camrec, *R.ad);
+            else if (R.ad)
+                hipLaunchKernelGGL((pt_rays_wf<WF_STACK, false, false, WfAdapt>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, ry,
+                                   P.camrec, *R.ad);
+            else if (s.has_leaf_table)
                 hipLaunchKernelGGL((pt_rays_wf<WF_STACK, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, ry, P.camrec);
             else
                 hipLaunchKernelGGL((pt_rays_wf<WF_STACK, false>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, ry, P.camrec);
@@ -1012,8 +1023,10 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
 // pnrt_render_adaptive's frames: the batches over the active tiles' path slots.  The
 // call has waited for everything in flight, so it is a lone call: the last call's pipe
 // (its primary records likely still valid, PrimKey), the caller's stream.
+// rays: pnrt_render_rays_adaptive's call -- the caller's sets as render_wavefront takes them; the batches trace
+// the list's camera rays into the pipe's per-slot records and leave its per-pixel ones and their key alone.
 static int render_adaptive(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const WfAdapt& ad, uint32_t chunk,
-                           uint32_t first, uint32_t nf) {
+                           uint32_t first, uint32_t nf, const float4* rays = nullptr, int64_t ray_stride = 0) {
     int rc;
     if ((rc = pipes_init(c)) || (rc = trace_grid_init(c))) return rc;
     const size_t pix = (size_t)fp.rows * c->width;
@@ -1023,11 +1036,16 @@ static int render_adaptive(pnrt_ctx* c, const DevScene& s, const FrameParams& fp
     c->last_pipe = (unsigned)(&P - c->pipe);
     const OvfSize ovf = ovf_size(c);
     if ((rc = pipe_size(c, P, pix, per_frame * 16 * chunk, per_frame * chunk, ovf.bytes))) return rc;
+    if (rays && (rc = P.camrec.reserve(c, per_frame * chunk * CAM_REC_BYTES))) return rc;
     ++c->ncall;
     hipStream_t w = (alone && WF_ALONE_ON_CALLER) ? c->stream : P.w;
     P.stage_set = false;
-    if ((rc = ensure_primary(c, s, fp, w, P.ovf, ovf.stride, P.primary, P.prim))) return rc;
-    const BatchRoute R = {w, alone, c->serial, false, ovf.stride, (c->width + 7) / 8, &ad, nullptr, nullptr, 0};
+    if (!rays && (rc = ensure_primary(c, s, fp, w, P.ovf, ovf.stride, P.primary, P.prim))) return rc;
+    if (rays && w != c->stream) {   // (render_wavefront's order: the caller's writes of the rays before the worker's reads)
+        HIPCHK(c, hipEventRecord(P.ev_rays, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(w, P.ev_rays, 0));
+    }
+    const BatchRoute R = {w, alone, c->serial, false, ovf.stride, (c->width + 7) / 8, &ad, nullptr, rays, ray_stride};
     return run_batches(c, s, fp, P, R, per_frame, chunk, first, nf);
 }
 
@@ -2394,16 +2412,21 @@ int pnrt_convergence(pnrt_ctx* c, float threshold, int band, int nsh, int shard,
     return check_fault(c);
 }
 
-int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float threshold, uint32_t min_frames, int band, int nsh,
-                         int shard, pnrt_adaptive_stats* out) {
+// pnrt_render_adaptive (rays: false -- the pnrt_set_frame camera) and pnrt_render_rays_adaptive (the caller's sets,
+// pnrt_render_rays' buffer rules) as `who`.
+static int adaptive_call(pnrt_ctx* c, const char* who, uint32_t first, uint32_t nf, float threshold, uint32_t min_frames, int band,
+                         int nsh, int shard, pnrt_adaptive_stats* out, bool rays = false, const void* ray_buf = nullptr,
+                         int64_t ray_stride = 0) {
     if (!c) return PNRT_E_ARG;
-    if (int rc = need_scene_frame(c, "render_adaptive")) return rc;
+    if (int rc = need_scene_frame(c, who)) return rc;
     if (!std::isfinite(threshold) || !(threshold >= 0.0f))
-        return set_err(c, PNRT_E_ARG, "render_adaptive: threshold must be finite and >= 0");
-    if (int rc = check_selector(c, "render_adaptive", band, nsh, shard)) return rc;
-    if (int rc = check_frame_range(c, "render_adaptive", first, nf)) return rc;
-    if (int rc = need_moments(c, "render_adaptive")) return rc;
-    if (c->kernel == 1) return set_err(c, PNRT_E_STATE, "render_adaptive: PNRT_KERNEL_V1 has no per-frame colours");
+        return set_err(c, PNRT_E_ARG, std::string(who) + ": threshold must be finite and >= 0");
+    if (int rc = check_selector(c, who, band, nsh, shard)) return rc;
+    if (int rc = check_frame_range(c, who, first, nf)) return rc;
+    if (rays)
+        if (int rc = check_ray_buffer(c, who, ray_buf, ray_stride, nf)) return rc;
+    if (int rc = need_moments(c, who)) return rc;
+    if (c->kernel == 1) return set_err(c, PNRT_E_STATE, std::string(who) + ": PNRT_KERNEL_V1 has no per-frame colours");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_all(c));                      // the predicate reads the moments as every earlier call left them
     if (int rc = check_fault(c)) return rc;
@@ -2415,7 +2438,7 @@ int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float thresho
     st.n_tiles = (int64_t)n_tiles;
     WfAdapt ad{};
     if (n_tiles) {
-        if (n_tiles > 0x7FFFFFFFull) return set_err(c, PNRT_E_ARG, "render_adaptive: frame too large");
+        if (n_tiles > 0x7FFFFFFFull) return set_err(c, PNRT_E_ARG, std::string(who) + ": frame too large");
         int rc;
         if ((rc = c->ad_masks.reserve(c, n_tiles * 8)) || (rc = c->ad_flags.reserve(c, n_tiles * 4)) ||
             (rc = c->ad_offs.reserve(c, n_tiles * 4)) || (rc = c->ad_list.reserve(c, n_tiles * sizeof(WfTile))) ||
@@ -2438,7 +2461,8 @@ int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float thresho
         HIPCHK(c, hipMemcpyAsync(&cnt, c->ad_counts, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
         if (int rc2 = mark_stream(c)) return rc2;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if ((size_t)cnt.n_active_tiles > n_tiles) return set_err(c, PNRT_E_HIP, "render_adaptive: the active-tile count is out of range");
+        if ((size_t)cnt.n_active_tiles > n_tiles)
+            return set_err(c, PNRT_E_HIP, std::string(who) + ": the active-tile count is out of range");
         st.n_active_pixels = (int64_t)cnt.n_active_pixels;
         st.n_active_tiles = (int64_t)cnt.n_active_tiles;
         ad.tiles = c->ad_list;
@@ -2446,17 +2470,28 @@ int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float thresho
     }
     uint32_t chunk = 0;
     if (nf > 0 && ad.n_tiles > 0) {
-        // the plan runs on the active tiles' slots: the colours are compact, 16 bytes per slot
+        // the plan runs on the active tiles' slots: the colours are compact, 16 bytes per slot (a ray call's slots
+        // hold their camera-ray records besides)
         const size_t per_frame = (size_t)ad.n_tiles * 64;
-        chunk = plan_chunk(c, per_frame, per_frame, nf);
-        if (chunk == 0) return set_err(c, PNRT_E_ARG, "render_adaptive: frame too large for one batch");
+        chunk = plan_chunk(c, per_frame, per_frame, nf, rays ? CAM_REC_BYTES : 0);
+        if (chunk == 0) return set_err(c, PNRT_E_ARG, std::string(who) + ": frame too large for one batch");
         st.frames_per_batch = chunk;
         st.n_batches = nf / chunk + (nf % chunk ? 1u : 0u);
     }
     if (out) *out = st;
     if (chunk == 0) return PNRT_OK;              // nothing to render: nothing queued
     DevScene s = launch_scene(c);
-    return render_adaptive(c, s, fp, ad, chunk, first, nf);
+    return render_adaptive(c, s, fp, ad, chunk, first, nf, static_cast<const float4*>(ray_buf), ray_stride);
+}
+
+int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float threshold, uint32_t min_frames, int band, int nsh,
+                         int shard, pnrt_adaptive_stats* out) {
+    return adaptive_call(c, "render_adaptive", first, nf, threshold, min_frames, band, nsh, shard, out);
+}
+
+int pnrt_render_rays_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, const void* rays, int64_t stride, float threshold,
+                              uint32_t min_frames, int band, int nsh, int shard, pnrt_adaptive_stats* out) {
+    return adaptive_call(c, "render_rays_adaptive", first, nf, threshold, min_frames, band, nsh, shard, out, true, rays, stride);
 }
 
 int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_params* params, pnrt_reproject_stats* out) {

@@ -29,9 +29,15 @@ PN_DEV bool ray_record_valid(const float4& o, const float4& d) {
 // writes the frame colour (0, 0, 0) and starts no path.
 // PIX: the record of pixel (x, lr) goes to rec[3 * (lr * width + x)], the per-pixel order
 // pt_guides reads (pnrt_render_guides_rays: one frame, the whole image), not to its slot.
-template <int STK, bool TBL, bool PIX = false>
+// AD: empty, or WfAdapt -- the slots of an adaptive ray batch (pnrt_render_rays_adaptive; DESIGN.md
+// section 30), through its list.  A wave is still one 8x8 tile of one frame; a lane whose mask bit
+// is clear is a lane beyond the edge: never stepped as a busy lane, no record.
+template <int STK, bool TBL, bool PIX = false, class... AD>
 __global__ void __launch_bounds__(WF_TRACE_BLOCK, PT_PRIM_WF_WAVES) pt_rays_wf(DevScene s, FrameParams fp, WfBufs b, WfRays ry,
-                                                                            float4* rec) {
+                                                                            float4* rec, AD... adv) {
+    constexpr bool ADAPT = wf_pack_is<WfAdapt, AD...>;
+    static_assert(!(ADAPT && PIX), "an adaptive batch's records go to their slots");
+    [[maybe_unused]] const WfAdapt ad = wf_adapt(adv...);
     __shared__ uint2 lds[(STK + 1) * WF_TRACE_BLOCK];     // STK depths + the spare one (wf_push)
     const __amdgpu_buffer_rsrc_t geo =
         __builtin_amdgcn_make_buffer_rsrc((void*)s.nodes, (short)0, (int)s.geo_bytes, 0x00020000);
@@ -41,8 +47,10 @@ __global__ void __launch_bounds__(WF_TRACE_BLOCK, PT_PRIM_WF_WAVES) pt_rays_wf(D
         // (wave-uniform: the loop's step and n are multiples of 64)
         if (i >= n) continue;
         int px, lr, k;
-        wf_coords(b, (uint32_t)i, px, lr, k);
-        const bool mine = px < fp.width && lr < fp.rows;
+        bool active = true;
+        if constexpr (ADAPT) active = wf_coords_adaptive_wave(b, ad, (uint32_t)i, px, lr, k);
+        else wf_coords(b, (uint32_t)i, px, lr, k);
+        const bool mine = active && px < fp.width && lr < fp.rows;
         const int py = shard_row(mine ? lr : 0, fp.band, fp.n_shards, fp.shard);
         // (a lane beyond the edge reads the record of column 0 of its frame's first row, unused)
         const float4* r = wf_ray_record(b, fp, ry, k, mine ? px : 0, py);

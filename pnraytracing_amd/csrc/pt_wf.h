@@ -211,21 +211,24 @@ struct WfRays {
     const float4* rays;          // the batch's first set
     int64_t frame_stride;        // records between the sets of consecutive frames (0: one set)
 };
-// the kernels' trailing argument pack: nothing (no list), the list, the camera table or the rays
-PN_DEV WfAdapt wf_adapt() { return WfAdapt{nullptr, 0u}; }
-PN_DEV WfAdapt wf_adapt(const WfAdapt& ad) { return ad; }
-PN_DEV WfAdapt wf_adapt(const WfCams&) { return WfAdapt{nullptr, 0u}; }
-PN_DEV WfAdapt wf_adapt(const WfRays&) { return WfAdapt{nullptr, 0u}; }
-PN_DEV WfCams wf_cams() { return WfCams{nullptr}; }
-PN_DEV WfCams wf_cams(const WfAdapt&) { return WfCams{nullptr}; }
-PN_DEV WfCams wf_cams(const WfCams& cm) { return cm; }
-PN_DEV WfCams wf_cams(const WfRays&) { return WfCams{nullptr}; }
-PN_DEV WfRays wf_rays() { return WfRays{nullptr, 0}; }
-PN_DEV WfRays wf_rays(const WfAdapt&) { return WfRays{nullptr, 0}; }
-PN_DEV WfRays wf_rays(const WfCams&) { return WfRays{nullptr, 0}; }
-PN_DEV WfRays wf_rays(const WfRays& ry) { return ry; }
+// the kernels' trailing argument pack: nothing (no list), the list, the camera table, the rays, or the
+// list and the rays (an adaptive ray batch, pnrt_render_rays_adaptive).  wf_pack_get: the pack's T, or
+// `none` where it holds no T.
 template <class T, class... AD>
 inline constexpr bool wf_pack_is = (std::is_same_v<T, AD> || ...);
+template <class T>
+PN_DEV T wf_pack_get(const T& none) { return none; }
+template <class T, class A, class... AD>
+PN_DEV T wf_pack_get(const T& none, const A& a, const AD&... rest) {
+    if constexpr (std::is_same_v<T, A>) return a;
+    else return wf_pack_get<T>(none, rest...);
+}
+template <class... AD>
+PN_DEV WfAdapt wf_adapt(const AD&... adv) { return wf_pack_get(WfAdapt{nullptr, 0u}, adv...); }
+template <class... AD>
+PN_DEV WfCams wf_cams(const AD&... adv) { return wf_pack_get(WfCams{nullptr}, adv...); }
+template <class... AD>
+PN_DEV WfRays wf_rays(const AD&... adv) { return wf_pack_get(WfRays{nullptr, 0}, adv...); }
 // -> whether the slot's pixel is active (a lane of an inactive pixel starts no path)
 PN_DEV bool wf_coords_adaptive(const WfBufs& b, const WfAdapt& ad, uint32_t s, int& x, int& lr, int& k) {
     uint32_t per_tile = 64u * (uint32_t)b.chunk_frames;
@@ -237,6 +240,23 @@ PN_DEV bool wf_coords_adaptive(const WfBufs& b, const WfAdapt& ad, uint32_t s, i
     x = tx * 8 + (p & 7);
     lr = ty * 8 + (p >> 3);
     return ((e.mask >> p) & 1ull) != 0ull;
+}
+// ... where the 64 slots of the lane's wave start at a multiple of 64 (the trace kernels' loops): they are
+// one tile of one frame, so the entry is one 16-byte scalar load for the wave, not 64 vector loads (read
+// through the constant address space, as wf_camera_dir reads its table: no kernel of the batch writes the list)
+PN_DEV bool wf_coords_adaptive_wave(const WfBufs& b, const WfAdapt& ad, uint32_t s, int& x, int& lr, int& k) {
+    typedef const uint32_t __attribute__((address_space(4))) cu32;
+    uint32_t per_tile = 64u * (uint32_t)b.chunk_frames;
+    uint32_t a = __builtin_amdgcn_readfirstlane(s / per_tile), rem = s - a * per_tile;
+    k = (int)(rem >> 6);
+    int p = (int)(rem & 63u);
+    cu32* e = (cu32*)(ad.tiles + PT_CHECK(b.fault, a, ad.n_tiles, PT_SITE_TILE));
+    const uint32_t tile = e[0];
+    const unsigned long long mask = (unsigned long long)e[2] | ((unsigned long long)e[3] << 32);
+    int ty = (int)(tile / (uint32_t)b.tiles_x), tx = (int)(tile - (uint32_t)ty * b.tiles_x);
+    x = tx * 8 + (p & 7);
+    lr = ty * 8 + (p >> 3);
+    return ((mask >> p) & 1ull) != 0ull;
 }
 
 // Number of set bits of m below this lane (v_mbcnt).
@@ -720,7 +740,8 @@ PN_DEV void wf_enqueue(const WfBufs& b, uint32_t i, uint32_t nfl, const BounceRa
 // AD: empty (pt_wf_gen_setup<>, the slots of a pnrt_render batch: the kernel's five
 // arguments), WfAdapt (the slots of an adaptive batch, through its list), WfCams (a
 // camera batch: `primary` holds a record per slot, V comes from the frame's camera) or
-// WfRays (a ray batch: a record per slot, V comes from the caller's ray).
+// WfRays (a ray batch: a record per slot, V comes from the caller's ray); WfAdapt, WfRays
+// together: an adaptive ray batch -- the list's slots, a record and a compact colour per slot.
 template <class... AD>
 __global__ void __launch_bounds__(256, WF_GEN_WAVES) pt_wf_gen_setup(DevScene s, FrameParams fp, WfBufs b, const float4* primary,
                                                        float4* colors, AD... adv) {

@@ -106,6 +106,11 @@ class ShardedFrame:
         """``render`` from caller rays (``PathTracer.render_rays``; the buffer covers the whole image) over this rank's rows."""
         self.tracer.render_rays(first_frame, n_frames, rays, frame_stride, self.band, self.world, self.rank)
 
+    def render_rays_adaptive(self, first_frame: int, n_frames: int, rays, frame_stride: int, threshold: float, min_frames: int = 8):
+        """``PathTracer.render_rays_adaptive`` over this rank's rows (local-row tiles); returns this rank's statistics."""
+        return self.tracer.render_rays_adaptive(first_frame, n_frames, rays, frame_stride, threshold, min_frames, self.band,
+                                                self.world, self.rank)
+
     def _gather(self) -> torch.Tensor | None:
         """Pack this rank's rows, gather on rank 0; returns the H x W x 4 image
         (row 0 = bottom) on rank 0 and None elsewhere."""

@@ -128,8 +128,8 @@ class InteractiveSession:
         self._model = (name, float(fov_deg), int(bool(per_pixel)))
 
     def _model_rays(self, cam, n: int, jitter: bool = True):
-        """(rays, frame_stride) of frames frame_count .. + n - 1 for the camera model."""
-        name, fov, per_pixel = self._model
+        """(rays, frame_stride) of frames frame_count .. + n - 1 for the camera model (none set: the pinhole model's)."""
+        name, fov, per_pixel = self._model if self._model is not None else ("pinhole", 180.0, 0)
         aa, radius, focus = self._lens if (self._lens is not None and jitter) else (0.0, 0.0, None)
         lens = radius > 0 and focus is not None
         still = not (aa > 0 or lens)                 # no sample: one set serves every frame
@@ -206,9 +206,12 @@ class InteractiveSession:
         ``frame_count``, until a call finds no pixel active -- every pixel of the image has
         ``max(min_frames, 2)`` frames and a relative standard error of at most ``threshold``
         (``PathTracer.render_adaptive``) -- or until this call has issued ``max_frames``
-        frames.  Converged pixels receive no more frames.  Enables the sample moments
-        itself.  Returns (the last call's statistics -- None when ``max_frames`` left no
-        call --, frames issued)."""
+        frames.  Converged pixels receive no more frames.  With ``set_camera_model`` or
+        ``set_lens`` in force every call makes its frames' rays (the lens alone: the
+        ``"pinhole"`` model's, the frames ``set_camera_model("pinhole")`` renders) and goes
+        through ``PathTracer.render_rays_adaptive``.  Enables the sample moments itself.
+        Returns (the last call's statistics -- None when ``max_frames`` left no call --,
+        frames issued)."""
         if frames_per_call < 1:
             raise ValueError("render_adaptive_until: frames_per_call must be >= 1")
         self.pt.enable_moments(True)
@@ -217,7 +220,11 @@ class InteractiveSession:
             n = min(frames_per_call, max_frames - done)
             cam = self.camera.uniforms()
             self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
-            stats = self.pt.render_adaptive(self.frame_count, n, threshold, min_frames)
+            if self._model is not None or self._lens is not None:
+                rays, stride = self._model_rays(cam, n)
+                stats = self.pt.render_rays_adaptive(self.frame_count, n, rays, stride, threshold, min_frames)
+            else:
+                stats = self.pt.render_adaptive(self.frame_count, n, threshold, min_frames)
             if stats["n_active_pixels"] == 0:        # nothing was rendered: the frames were not issued
                 break
             self._rendered_camera = cam
@@ -252,7 +259,9 @@ class InteractiveSession:
         sample moments itself and advances ``frame_count`` by ``n``.  With ``set_lens`` the
         frames are ``render_cameras``'s instead: frame ``frame_count + k`` with its camera of
         the sequence, blended at the weight of that frame number (the statistics then
-        report every pixel active and the call's batch plan)."""
+        report every pixel active and the call's batch plan).  The per-pixel-count form
+        of those frames is ``PathTracer.render_rays_adaptive`` with ``threshold 0,
+        min_frames 0xFFFFFFFF``."""
         self.pt.enable_moments(True)
         cam = self.camera.uniforms()
         self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)

@@ -503,6 +503,25 @@ class PathTracer:
                                                 shard, ctypes.byref(st)), "pnrt_render_adaptive")
         return {f: getattr(st, f) for f, _ in st._fields_}
 
+    def render_rays_adaptive(self, first: int, n: int, rays, frame_stride: int, threshold: float, min_frames: int = 8,
+                             band: int = 1, n_shards: int = 1, shard: int = 0) -> dict:
+        """``render_adaptive`` over caller rays (pnrt_render_rays_adaptive): the active pixels
+        receive the frames ``render_rays`` would render from ``rays`` / ``frame_stride`` (its
+        buffer rules; the records of inactive pixels do not matter), folded at the weight of
+        the pixel's own count.  ``threshold 0, min_frames 0xFFFFFFFF`` makes every pixel
+        active.  Returns the fields of ``pnrt_adaptive_stats``."""
+        for name, v in (("first", first), ("n", n), ("min_frames", min_frames)):
+            if not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError(f"render_rays_adaptive: {name} = {v} is outside 0 .. 2**32 - 1")
+        if not -2 ** 63 <= frame_stride < 2 ** 63:
+            raise ValueError(f"render_rays_adaptive: frame_stride = {frame_stride} does not fit 64 bits")
+        ptr = 0 if rays is None else self._rays_ptr(rays)
+        st = N.AdaptiveStats()
+        self._ck(self._lib.pnrt_render_rays_adaptive(self._ctx, first, n, ctypes.c_void_p(ptr), frame_stride,
+                                                     ctypes.c_float(threshold), min_frames, band, n_shards, shard, ctypes.byref(st)),
+                 "pnrt_render_rays_adaptive")
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
     def reproject(self, from_camera: np.ndarray, normal_min: float | None = None, position_tolerance: float | None = None,
                   max_history: int | None = None) -> dict:
         """After a camera move: resample the accumulation and the moments from the view

@@ -16,7 +16,20 @@ Reported, not asserted.
                  range's, per pixel), lens and pixel-filter samples per frame (per_pixel 0)
                  against per pixel (1), raw and under pnrt_denoise_variance.
 
-usage: python tools/rays_bench.py cost cameras|rays [out.json] | quality [out.json]"""
+  adaptive       pnrt_render_rays_adaptive (results in profiles/rays_adaptive/):
+                 C2 at 1920x1080, 16-frame calls of a set per frame with that lens, the moments on,
+                 the host clock around a call and the synchronise that ends it.  Every repetition
+                 starts from the same state -- 64 frames of pnrt_render_rays on the lens sets, made
+                 again outside the clock -- so the mask is the same in every repetition and in both
+                 builds.  `yardstick` (any library with pnrt_render_rays and pnrt_render_adaptive:
+                 the parent commit's build through PNRT_DEVICE_LIB): pnrt_render_rays, and
+                 pnrt_render_adaptive at the thresholds that leave half and a quarter of the tiles
+                 active.  `this`: pnrt_render_rays_adaptive with every tile active and at those two
+                 thresholds.  Two warm-up repetitions, then median, minimum and maximum of five;
+                 `profile`: the per-class profile of one call of each of this tree's variants, alone.
+
+usage: python tools/rays_bench.py cost cameras|rays [out.json] | quality [out.json] |
+                                  adaptive yardstick|this|profile [out.json]"""
 import json
 import os
 import statistics
@@ -127,12 +140,86 @@ def quality(w=512, h=512, counts=(4, 16, 64), long_frames=4096):
     return res
 
 
+def adaptive(which, w=1920, h=1080, frames=16, reps=5, warm=2):
+    cfg = scenes.bunny_c2(width=w, height=h, spp=1)
+    res = {"size": f"{w}x{h}", "frames_per_call": frames, "state_frames": 64}
+    pix = w * h
+    ALL = 0xFFFFFFFF
+    with PathTracer(0) as pt:
+        import torch
+        res["library"] = pt.version()
+        pt.load(cfg)
+        focus, _ = focus_on_bunny(pt, cfg, w, h)
+        lens = {"aa_width": 1.0, "lens_radius": RADIUS, "focus_distance": focus}
+        buf = torch.empty((frames * pix, 8), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        pt.enable_moments(True)
+
+        def restart():
+            """64 frames of the lens sets, then the call's own sets (frames 64 ..) in the buffer."""
+            pt.reset_accum()
+            for f in range(0, 64 + frames, frames):
+                pt.make_rays("pinhole", cfg.camera, f, frames, pix, out=buf, **lens)
+                if f < 64:
+                    pt.render_rays(f, frames, buf, pix)
+            pt.synchronize()
+
+        def threshold_for(share):                    # the active-tile share falls with the threshold
+            lo, hi = 0.0, 1.0
+            for _ in range(14):
+                mid = (lo + hi) / 2
+                st = pt.render_adaptive(64, 0, mid, 2)
+                lo, hi = (mid, hi) if st["n_active_tiles"] / st["n_tiles"] > share else (lo, mid)
+            return hi
+
+        restart()
+        thr = {"half": threshold_for(0.5), "quarter": threshold_for(0.25)}
+        res["thresholds"] = thr
+        if which == "yardstick":
+            variants = {"render_rays": lambda: pt.render_rays(64, frames, buf, pix),
+                        "render_adaptive_half": lambda: pt.render_adaptive(64, frames, thr["half"], 2),
+                        "render_adaptive_quarter": lambda: pt.render_adaptive(64, frames, thr["quarter"], 2)}
+        else:
+            variants = {"rays_adaptive_all": lambda: pt.render_rays_adaptive(64, frames, buf, pix, 0.0, ALL),
+                        "rays_adaptive_half": lambda: pt.render_rays_adaptive(64, frames, buf, pix, thr["half"], 2),
+                        "rays_adaptive_quarter": lambda: pt.render_rays_adaptive(64, frames, buf, pix, thr["quarter"], 2)}
+
+        def repetition(call):
+            restart()
+            t0 = time.perf_counter()
+            st = call()
+            pt.synchronize()
+            return (time.perf_counter() - t0) * 1e3, st
+
+        for name, call in variants.items():
+            if which == "profile":
+                repetition(call)
+                restart()
+                pt.profile_enable(True)
+                st = call()
+                pt.synchronize()
+                prof = pt.profile_read()
+                pt.profile_enable(False)
+                res[name] = {"profile_ms": {k: v[0] for k, v in prof.items() if v[1]},
+                             "profile_launches": {k: v[1] for k, v in prof.items() if v[1]}, "stats": st}
+                continue
+            runs = [repetition(call) for _ in range(warm + reps)][warm:]
+            ms = [r[0] for r in runs]
+            res[name] = {"ms_per_call": {"median": statistics.median(ms), "min": min(ms), "max": max(ms)}, "all_ms": ms,
+                         "stats": runs[-1][1]}
+    return res
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else ""
     if what == "cost" and len(sys.argv) > 2 and sys.argv[2] in ("cameras", "rays"):
         out = {"cost": [cost_at(sys.argv[2], 1920, 1080, 16, 4, False), cost_at(sys.argv[2], 512, 512, 1, 32, True)]}
         for c in out["cost"]:
             print(c["size"], json.dumps({v: {k: c[v][k] for k in c[v] if k != "all_ms"} for v in c if isinstance(c[v], dict)}))
+        path = sys.argv[3] if len(sys.argv) > 3 else None
+    elif what == "adaptive" and len(sys.argv) > 2 and sys.argv[2] in ("yardstick", "this", "profile"):
+        out = {"adaptive": adaptive(sys.argv[2])}
+        print(json.dumps({k: ({q: v[q] for q in v if q != "all_ms"} if isinstance(v, dict) else v) for k, v in out["adaptive"].items()}))
         path = sys.argv[3] if len(sys.argv) > 3 else None
     elif what == "quality":
         out = {"quality": quality()}
