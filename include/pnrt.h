@@ -315,8 +315,8 @@ int pnrt_cameras_batch_plan(pnrt_ctx* ctx, uint32_t n_frames, int band_rows, int
  * first_frame + n_frames > 0xFFFFFFFF; PNRT_E_TRACE as pnrt_render.  n_frames == 0 or a
  * shard without rows: PNRT_OK, nothing queued.
  * The adaptive variant is pnrt_render_rays_adaptive.
- * Out of scope: pnrt_reproject across ray sets, a host-array form, a tMax or near clip
- * per ray. */
+ * Out of scope: reprojection across arbitrary ray sets (the views of pnrt_make_rays' four
+ * models go through pnrt_reproject_view), a host-array form, a tMax or near clip per ray. */
 typedef struct { float origin[3], reserved0, direction[3], reserved1; } pnrt_ray;   /* 32 bytes */
 int pnrt_render_rays(pnrt_ctx* ctx, uint32_t first_frame, uint32_t n_frames, const void* rays_dev, int64_t frame_stride,
                      int band_rows, int n_shards, int shard);
@@ -691,6 +691,46 @@ typedef struct {
 } pnrt_reproject_stats;           /* 48 bytes */
 int pnrt_reproject(pnrt_ctx* ctx, const pnrt_camera* from,
                    const pnrt_reproject_params* params, pnrt_reproject_stats* out /* may be NULL */);
+
+/* pnrt_reproject with both views given as camera models (bit for
+ * bit): `from` is the view the accumulation was rendered with, `to` the view to continue
+ * in.  Each view is the centre rays of its model -- what pnrt_make_rays writes for it with
+ * aa_width 0 and lens_radius 0, the same for every frame.  aa_width, lens_radius,
+ * focus_distance and per_pixel are validated as pnrt_make_rays validates them and otherwise
+ * ignored.  The pnrt_set_frame camera is ignored and stays current; frame size, scene and
+ * traversal mode are the current ones.  Whole image, synchronous: the call waits for the
+ * calls in flight, as pnrt_reproject does.
+ *   Every pixel of `to` whose centre ray hits is mapped into `from`'s image by the inverse
+ * of `from`'s model -- the pinhole's image-plane algebra (pnrt_reproject's), the
+ * orthographic projection, or the direction's angles (PN-libm's atan2) for the
+ * equirectangular and the fisheye view -- and takes pnrt_reproject's four bilinear taps
+ * there, with its validity tests, its blend, its capped count and its statistics.  The
+ * position test measures against |P - eye_from|, the orthographic view against P's depth
+ * along the view direction.  An equirectangular `from` wraps in x: a point beyond column
+ * width - 1 takes its right taps from column 0 (rows do not wrap).  A pixel of `to` without
+ * a ray (a fisheye's corners) is a primary miss: counted in n_missed, started at zero.  A
+ * pixel of `from` without a ray holds no history: a tap on it is invalid.
+ *   The call makes the centre rays of `from` in a buffer of the context (width * height
+ * records, allocated by the first call; one pnrt_make_rays launch, PNRT_K_BLEND), renders
+ * their guide images as pnrt_render_guides_rays does (one PNRT_K_PRIMARY launch) and keeps
+ * the position and normal images as the history; then the same for `to`.  Guide images
+ * made from rays carry no camera, so the library cannot tell that the current ones belong
+ * to `from`: both views' are always rendered -- no lent records, no key match.  On return
+ * the guide images are what pnrt_make_rays(to's centre rays) and pnrt_render_guides_rays
+ * leave, bit for bit, valid under that call's rules: pnrt_denoise* needs no further call.
+ * pnrt_accum_device_ptr, pnrt_moments_device_ptr and pnrt_aov_device_ptr return what they
+ * returned before, the moments still cover the accumulation, and the kept per-pixel
+ * camera-ray records are left alone.  Continue with pnrt_render_rays_adaptive (threshold
+ * 0, min_frames 0xFFFFFFFF: every pixel, each at its own count's weight).
+ *   PNRT_E_STATE and the `params` errors are pnrt_reproject's; PNRT_E_ARG for from or to
+ * NULL and for every argument rule of pnrt_make_rays broken by either (the message names
+ * which of the two); PNRT_E_TRACE as pnrt_read_accum returns it.  A refusal changes
+ * nothing.
+ *   Not provided: a from / to given as ray buffers (an arbitrary ray set has no inverse);
+ * sample-aware reprojection (jitter, lens); sharded or multi-GPU reprojection; reuse or
+ * lending of guide records for model views. */
+int pnrt_reproject_view(pnrt_ctx* ctx, const pnrt_ray_camera* from, const pnrt_ray_camera* to,
+                        const pnrt_reproject_params* params, pnrt_reproject_stats* out /* may be NULL */);
 
 /* The display transform (not in the reference, whose render.frag shows the clamped
  * accumulation, and whose GL blit stays out of scope): one of the context's float

@@ -266,6 +266,8 @@ def _type_device(lib):
     _sig(lib, "pnrt_render_adaptive", INT, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32, INT, INT, INT,
          ctypes.POINTER(AdaptiveStats))
     _sig(lib, "pnrt_reproject", INT, P, ctypes.POINTER(Camera), ctypes.POINTER(ReprojectParams), ctypes.POINTER(ReprojectStats))
+    _sig(lib, "pnrt_reproject_view", INT, P, ctypes.POINTER(RayCamera), ctypes.POINTER(RayCamera), ctypes.POINTER(ReprojectParams),
+         ctypes.POINTER(ReprojectStats))
     _sig(lib, "pnrt_display", INT, P, ctypes.POINTER(DisplayParams))
     _sig(lib, "pnrt_read_display", INT, P, U8)
     _sig(lib, "pnrt_display_device_ptr", P, P)

@@ -29,7 +29,8 @@ ROCM = "/opt/rocm"             # headers and libraries of the HIP runtime and RC
 DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
                "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pt_adaptive.h", "pt_query.h", "pn_math.h",
-               "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h", "pt_display.h", "pt_refit.h", "pt_cameras.h", "pt_rays.h"]
+               "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h", "pt_display.h", "pt_refit.h", "pt_cameras.h", "pt_rays.h",
+               "pt_reproject_view.h"]
 
 
 def _run(cmd, cwd=None):
@@ -129,6 +130,7 @@ ABI_CALLERS = {
     "c_abi_query.c": [],                     # ray queries, both kinds (tests/test_gpu_query_c_abi.py)
     "c_abi_denoise_variance.c": [],          # the variance-guided preview (tests/test_gpu_denoise_variance_c_abi.py)
     "c_abi_reproject.c": [],                 # temporal reprojection (tests/test_gpu_reproject_c_abi.py)
+    "c_abi_reproject_view.c": [],            # reprojection between camera models (tests/test_gpu_reproject_view_c_abi.py)
     "c_abi_display.c": [],                   # the display transform and auto exposure (tests/test_gpu_display_c_abi.py)
     # the multi-GPU caller: one process, one RCCL communicator per device (ncclCommInitAll + ncclGather)
     "c_abi_multigpu.cpp": ["-lpnrt_host", "-lamdhip64", "-lrccl"],

@@ -27,6 +27,7 @@
 #include "pt_adaptive.h"
 #include "pt_query.h"
 #include "pt_reproject.h"
+#include "pt_reproject_view.h"
 #include "pt_display.h"
 #include "pt_refit.h"
 #include "pt_cameras.h"
@@ -266,6 +267,7 @@ struct pnrt_ctx {
     DevBuf<float4> rp_acc, rp_mom;         // the resampled accumulation and moments, before they are
                                            // copied over the images themselves
     DevBuf<ReprojectCounts> rp_counts;     // the counts the host reads back
+    DevBuf<float4> rp_rays;                // pnrt_reproject_view: the centre rays of one view, then of the other
     // the display transform (pnrt_display; pt_display.h): none until the first call
     DevBuf<uint32_t> disp;                 // the RGBA8 display image
     int disp_width = 0, disp_height = 0;   // its size (0: none yet)
@@ -2155,12 +2157,9 @@ int pnrt_render_rays(pnrt_ctx* c, uint32_t first, uint32_t nf, const void* rays,
     return render_wavefront(c, s, fp, first, nf, nullptr, static_cast<const float4*>(rays), stride);
 }
 
-int pnrt_render_guides_rays(pnrt_ctx* c, const void* rays) {
-    if (!c) return PNRT_E_ARG;
-    if (int rc = need_scene_frame(c, "render_guides_rays")) return rc;
-    if (int rc = check_ray_buffer(c, "render_guides_rays", rays, 0)) return rc;
-    if (int rc = check_fault(c)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
+// The guide images of one ray set (pnrt_render_guides_rays; both views of pnrt_reproject_view): one trace of
+// class PNRT_K_PRIMARY into the guides' own record buffer, then pt_guides.  The checks are the caller's.
+static int render_guides_rays(pnrt_ctx* c, const void* rays) {
     int rc;
     if ((rc = pipes_init(c)) || (rc = trace_grid_init(c))) return rc;
     const DevScene s = launch_scene(c);
@@ -2200,27 +2199,42 @@ int pnrt_render_guides_rays(pnrt_ctx* c, const void* rays) {
     return mark_stream(c);
 }
 
+int pnrt_render_guides_rays(pnrt_ctx* c, const void* rays) {
+    if (!c) return PNRT_E_ARG;
+    if (int rc = need_scene_frame(c, "render_guides_rays")) return rc;
+    if (int rc = check_ray_buffer(c, "render_guides_rays", rays, 0)) return rc;
+    if (int rc = check_fault(c)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return render_guides_rays(c, rays);
+}
+
+// pnrt_make_rays' rules for its camera (`who`: the call, or the call and which of its views)
+static int check_ray_camera(pnrt_ctx* c, const std::string& who, const pnrt_ray_camera* cam) {
+    if (!cam) return set_err(c, PNRT_E_ARG, who + ": cam is NULL");
+    if (cam->model < PNRT_CAM_PINHOLE || cam->model > PNRT_CAM_FISHEYE) return set_err(c, PNRT_E_ARG, who + ": unknown model");
+    const float* cf = reinterpret_cast<const float*>(&cam->camera);
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(cf[i])) return set_err(c, PNRT_E_ARG, who + ": a camera component is not finite");
+    if (!std::isfinite(cam->fov_deg) || !std::isfinite(cam->focus_distance))
+        return set_err(c, PNRT_E_ARG, who + ": fov_deg or focus_distance is not finite");
+    if (cam->model == PNRT_CAM_FISHEYE && !(cam->fov_deg > 0.0f && cam->fov_deg <= 360.0f))
+        return set_err(c, PNRT_E_ARG, who + ": a fisheye's fov_deg must be in (0, 360]");
+    if (!(std::isfinite(cam->aa_width) && cam->aa_width >= 0.0f) || !(std::isfinite(cam->lens_radius) && cam->lens_radius >= 0.0f))
+        return set_err(c, PNRT_E_ARG, who + ": aa_width and lens_radius must be finite and >= 0");
+    if (cam->lens_radius > 0.0f && cam->model != PNRT_CAM_PINHOLE)
+        return set_err(c, PNRT_E_ARG, who + ": a lens needs PNRT_CAM_PINHOLE");
+    if (cam->lens_radius > 0.0f && !(cam->focus_distance > 0.0f))
+        return set_err(c, PNRT_E_ARG, who + ": a lens needs focus_distance > 0");
+    if (cam->per_pixel != 0 && cam->per_pixel != 1) return set_err(c, PNRT_E_ARG, who + ": per_pixel must be 0 or 1");
+    if (cam->reserved != 0) return set_err(c, PNRT_E_ARG, who + ": reserved must be 0");
+    return PNRT_OK;
+}
+
 int pnrt_make_rays(pnrt_ctx* c, const pnrt_ray_camera* cam, uint32_t first, uint32_t n_sets, void* out, int64_t stride) {
     if (!c) return PNRT_E_ARG;
     static_assert(sizeof(pnrt_ray) == 32 && sizeof(pnrt_ray_camera) == 76, "the documented sizes");
     if (!c->has_frame) return set_err(c, PNRT_E_STATE, "make_rays: set_frame first");
-    if (!cam) return set_err(c, PNRT_E_ARG, "make_rays: cam is NULL");
-    if (cam->model < PNRT_CAM_PINHOLE || cam->model > PNRT_CAM_FISHEYE) return set_err(c, PNRT_E_ARG, "make_rays: unknown model");
-    const float* cf = reinterpret_cast<const float*>(&cam->camera);
-    for (int i = 0; i < 12; ++i)
-        if (!std::isfinite(cf[i])) return set_err(c, PNRT_E_ARG, "make_rays: a camera component is not finite");
-    if (!std::isfinite(cam->fov_deg) || !std::isfinite(cam->focus_distance))
-        return set_err(c, PNRT_E_ARG, "make_rays: fov_deg or focus_distance is not finite");
-    if (cam->model == PNRT_CAM_FISHEYE && !(cam->fov_deg > 0.0f && cam->fov_deg <= 360.0f))
-        return set_err(c, PNRT_E_ARG, "make_rays: a fisheye's fov_deg must be in (0, 360]");
-    if (!(std::isfinite(cam->aa_width) && cam->aa_width >= 0.0f) || !(std::isfinite(cam->lens_radius) && cam->lens_radius >= 0.0f))
-        return set_err(c, PNRT_E_ARG, "make_rays: aa_width and lens_radius must be finite and >= 0");
-    if (cam->lens_radius > 0.0f && cam->model != PNRT_CAM_PINHOLE)
-        return set_err(c, PNRT_E_ARG, "make_rays: a lens needs PNRT_CAM_PINHOLE");
-    if (cam->lens_radius > 0.0f && !(cam->focus_distance > 0.0f))
-        return set_err(c, PNRT_E_ARG, "make_rays: a lens needs focus_distance > 0");
-    if (cam->per_pixel != 0 && cam->per_pixel != 1) return set_err(c, PNRT_E_ARG, "make_rays: per_pixel must be 0 or 1");
-    if (cam->reserved != 0) return set_err(c, PNRT_E_ARG, "make_rays: reserved must be 0");
+    if (int rc = check_ray_camera(c, "make_rays", cam)) return rc;
     if (int rc = check_frame_range(c, "make_rays", first, n_sets)) return rc;
     if (int rc = check_ray_buffer(c, "make_rays", out, stride, n_sets)) return rc;
     const size_t pix = (size_t)c->width * c->height;
@@ -2494,44 +2508,60 @@ int pnrt_render_rays_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, const vo
     return adaptive_call(c, "render_rays_adaptive", first, nf, threshold, min_frames, band, nsh, shard, out, true, rays, stride);
 }
 
-int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_params* params, pnrt_reproject_stats* out) {
-    if (!c) return PNRT_E_ARG;
-    if (int rc = need_scene_frame(c, "reproject")) return rc;
-    if (int rc = need_moments(c, "reproject")) return rc;
-    if (c->kernel == 1) return set_err(c, PNRT_E_STATE, "reproject: PNRT_KERNEL_V1 keeps no sample moments");
-    if (!from) return set_err(c, PNRT_E_ARG, "reproject: the camera the accumulation was rendered with is NULL");
-    for (const float* v : {from->eye, from->lower_left, from->horizontal, from->vertical})
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(v[k])) return set_err(c, PNRT_E_ARG, "reproject: a camera float is not finite");
-    pnrt_reproject_params p = {0.9f, 0.02f, 32u, 0u};        // the defaults (pnrt.h)
-    if (params) p = *params;
-    if (!std::isfinite(p.normal_min) || p.normal_min < -1.0f || p.normal_min > 1.0f)
-        return set_err(c, PNRT_E_ARG, "reproject: normal_min must be in [-1, 1]");
-    if (!std::isfinite(p.position_tolerance) || !(p.position_tolerance > 0.0f))
-        return set_err(c, PNRT_E_ARG, "reproject: position_tolerance must be finite and > 0");
-    if (p.max_history == 0u) return set_err(c, PNRT_E_ARG, "reproject: max_history must be >= 1");
-    if (p.reserved != 0u) return set_err(c, PNRT_E_ARG, "reproject: reserved must be 0");
+// ---- temporal reprojection (pt_reproject.h, pt_reproject_view.h; DESIGN.md sections 25 and 31) ------------
+// The state rules, then the parameter rules, that pnrt_reproject and pnrt_reproject_view share; *p: the
+// parameters in force.
+static int reproject_check_state(pnrt_ctx* c, const char* who) {
+    if (int rc = need_scene_frame(c, who)) return rc;
+    if (int rc = need_moments(c, who)) return rc;
+    if (c->kernel == 1) return set_err(c, PNRT_E_STATE, std::string(who) + ": PNRT_KERNEL_V1 keeps no sample moments");
+    return PNRT_OK;
+}
+static int reproject_check_params(pnrt_ctx* c, const char* who, const pnrt_reproject_params* params, pnrt_reproject_params* p) {
+    const std::string w(who);
+    *p = {0.9f, 0.02f, 32u, 0u};                 // the defaults (pnrt.h)
+    if (params) *p = *params;
+    if (!std::isfinite(p->normal_min) || p->normal_min < -1.0f || p->normal_min > 1.0f)
+        return set_err(c, PNRT_E_ARG, w + ": normal_min must be in [-1, 1]");
+    if (!std::isfinite(p->position_tolerance) || !(p->position_tolerance > 0.0f))
+        return set_err(c, PNRT_E_ARG, w + ": position_tolerance must be finite and > 0");
+    if (p->max_history == 0u) return set_err(c, PNRT_E_ARG, w + ": max_history must be >= 1");
+    if (p->reserved != 0u) return set_err(c, PNRT_E_ARG, w + ": reserved must be 0");
+    if ((size_t)c->width * c->height > 0xFFFFFFFFull / 64) return set_err(c, PNRT_E_ARG, w + ": frame too large");     // (render_guides' limit)
+    return PNRT_OK;
+}
+
+// Waits for the calls in flight (the images as every earlier call left them) and reserves the call's buffers.
+static int reproject_begin(pnrt_ctx* c) {
     const size_t pix = (size_t)c->width * c->height;
-    if (pix > 0xFFFFFFFFull / 64) return set_err(c, PNRT_E_ARG, "reproject: frame too large");     // (render_guides' limit)
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, sync_all(c));                      // the images as every earlier call left them
+    HIPCHK(c, sync_all(c));
     int rc;
     if ((rc = check_fault(c))) return rc;
     if ((rc = c->rp_pos.reserve(c, pix * 16)) || (rc = c->rp_nrm.reserve(c, pix * 16)) ||
         (rc = c->rp_acc.reserve(c, pix * 16)) || (rc = c->rp_mom.reserve(c, pix * 16)) ||
         (rc = c->rp_counts.reserve(c, REPROJECT_SLOTS * sizeof(ReprojectCounts))))
         return rc;
-    // the guide images of `from` (the current ones when they were rendered for it), kept as the history
-    if (!guide_key_eq(c->guide_key, guide_key_for(c, *from), /* camera_keyed */ true))
-        if ((rc = render_guides(c, *from))) return rc;
-    {
-        ProfScope ps(c, PNRT_K_BLEND);
-        HIPCHK(c, hipMemcpyAsync(c->rp_pos, c->aov[PNRT_AOV_POSITION], pix * 16, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->rp_nrm, c->aov[PNRT_AOV_NORMAL], pix * 16, hipMemcpyDeviceToDevice, c->stream));
-    }
-    if ((rc = render_guides(c, c->cam))) return rc;
+    return PNRT_OK;
+}
+
+// The current guide images become the history (rp_pos / rp_nrm): view A's.
+static int reproject_keep_history(pnrt_ctx* c) {
+    const size_t pix = (size_t)c->width * c->height;
+    ProfScope ps(c, PNRT_K_BLEND);
+    HIPCHK(c, hipMemcpyAsync(c->rp_pos, c->aov[PNRT_AOV_POSITION], pix * 16, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rp_nrm, c->aov[PNRT_AOV_NORMAL], pix * 16, hipMemcpyDeviceToDevice, c->stream));
+    return PNRT_OK;
+}
+
+// The kernel of view A's model over the history and the current guide images (view B's), the copies back and
+// the counts.  cam: view A's camera; fov_deg: a fisheye's.
+static int reproject_run(pnrt_ctx* c, const pnrt_reproject_params& p, int model, const pnrt_camera& cam, float fov_deg,
+                         pnrt_reproject_stats* out) {
+    const size_t pix = (size_t)c->width * c->height;
+    int rc;
     ReprojectArgs ra;
-    cam_floats(ra.eye, ra.llc, ra.hor, ra.ver, *from);
+    cam_floats(ra.eye, ra.llc, ra.hor, ra.ver, cam);
     ra.normal_min = p.normal_min; ra.position_tolerance = p.position_tolerance; ra.max_history = p.max_history;
     ra.width = c->width; ra.height = c->height;
     ra.tiles_x = (c->width + 7) / 8;
@@ -2540,10 +2570,26 @@ int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_pa
     HIPCHK(c, hipMemsetAsync(c->rp_counts, 0, REPROJECT_SLOTS * sizeof(ReprojectCounts), c->stream));
     {
         ProfScope ps(c, PNRT_K_BLEND);
-        hipLaunchKernelGGL(pt_reproject_kernel, dim3(std::min<uint32_t>(ra.n_tiles, REPROJECT_MAX_GRID)), dim3(REPROJECT_BLOCK), 0,
-                           c->stream, ra, (const float4*)c->accum, (const float4*)c->moments, (const float4*)c->rp_pos,
-                           (const float4*)c->rp_nrm, (const float4*)c->aov[PNRT_AOV_POSITION],
-                           (const float4*)c->aov[PNRT_AOV_NORMAL], c->rp_acc, c->rp_mom, c->rp_counts);
+        const dim3 grid(std::min<uint32_t>(ra.n_tiles, REPROJECT_MAX_GRID)), block(REPROJECT_BLOCK);
+        const float4 *acc = c->accum, *mom = c->moments, *pos_a = c->rp_pos, *nrm_a = c->rp_nrm;
+        const float4 *pos_b = c->aov[PNRT_AOV_POSITION], *nrm_b = c->aov[PNRT_AOV_NORMAL];
+        switch (model) {
+        case PNRT_CAM_ORTHO:
+            hipLaunchKernelGGL(pt_reproject_view_kernel<PT_CAM_ORTHO>, grid, block, 0, c->stream, ra, fov_deg, acc, mom, pos_a, nrm_a,
+                               pos_b, nrm_b, c->rp_acc.p, c->rp_mom.p, c->rp_counts.p);
+            break;
+        case PNRT_CAM_EQUIRECT:
+            hipLaunchKernelGGL(pt_reproject_view_kernel<PT_CAM_EQUIRECT>, grid, block, 0, c->stream, ra, fov_deg, acc, mom, pos_a,
+                               nrm_a, pos_b, nrm_b, c->rp_acc.p, c->rp_mom.p, c->rp_counts.p);
+            break;
+        case PNRT_CAM_FISHEYE:
+            hipLaunchKernelGGL(pt_reproject_view_kernel<PT_CAM_FISHEYE>, grid, block, 0, c->stream, ra, fov_deg, acc, mom, pos_a,
+                               nrm_a, pos_b, nrm_b, c->rp_acc.p, c->rp_mom.p, c->rp_counts.p);
+            break;
+        default:
+            hipLaunchKernelGGL(pt_reproject_kernel, grid, block, 0, c->stream, ra, acc, mom, pos_a, nrm_a, pos_b, nrm_b, c->rp_acc.p,
+                               c->rp_mom.p, c->rp_counts.p);
+        }
     }
     HIPCHK(c, hipGetLastError());
     {
@@ -2571,6 +2617,62 @@ int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_pa
         out->max_frames = cnt.max_frames;
     }
     return check_fault(c);
+}
+
+int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_params* params, pnrt_reproject_stats* out) {
+    if (!c) return PNRT_E_ARG;
+    pnrt_reproject_params p;
+    if (int rc = reproject_check_state(c, "reproject")) return rc;
+    if (!from) return set_err(c, PNRT_E_ARG, "reproject: the camera the accumulation was rendered with is NULL");
+    for (const float* v : {from->eye, from->lower_left, from->horizontal, from->vertical})
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(v[k])) return set_err(c, PNRT_E_ARG, "reproject: a camera float is not finite");
+    if (int rc = reproject_check_params(c, "reproject", params, &p)) return rc;
+    int rc;
+    if ((rc = reproject_begin(c))) return rc;
+    // the guide images of `from` (the current ones when they were rendered for it), kept as the history
+    if (!guide_key_eq(c->guide_key, guide_key_for(c, *from), /* camera_keyed */ true))
+        if ((rc = render_guides(c, *from))) return rc;
+    if ((rc = reproject_keep_history(c))) return rc;
+    if ((rc = render_guides(c, c->cam))) return rc;
+    return reproject_run(c, p, PNRT_CAM_PINHOLE, *from, 0.0f, out);
+}
+
+// The centre rays of `view` (aa_width 0, no lens: no sample, so any frame's) into the context's ray buffer, and
+// their guide images.
+static int reproject_view_guides(pnrt_ctx* c, const pnrt_ray_camera& view) {
+    const size_t pix = (size_t)c->width * c->height;
+    MakeRays m{};
+    cam_floats(m.eye, m.llc, m.hor, m.ver, view.camera);
+    m.model = view.model; m.fov_deg = view.fov_deg;
+    m.width = c->width; m.height = c->height;
+    m.n_sets = 1;
+    {
+        ProfScope ps(c, PNRT_K_BLEND);
+        hipLaunchKernelGGL(pt_make_rays_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, m, c->rp_rays.p);
+    }
+    HIPCHK(c, hipGetLastError());
+    return render_guides_rays(c, c->rp_rays.p);
+}
+
+int pnrt_reproject_view(pnrt_ctx* c, const pnrt_ray_camera* from, const pnrt_ray_camera* to, const pnrt_reproject_params* params,
+                        pnrt_reproject_stats* out) {
+    if (!c) return PNRT_E_ARG;
+    pnrt_reproject_params p;
+    if (int rc = reproject_check_state(c, "reproject_view")) return rc;
+    if (int rc = reproject_check_params(c, "reproject_view", params, &p)) return rc;
+    if (!from) return set_err(c, PNRT_E_ARG, "reproject_view: from (the view the accumulation was rendered with) is NULL");
+    if (!to) return set_err(c, PNRT_E_ARG, "reproject_view: to (the view to continue in) is NULL");
+    if (int rc = check_ray_camera(c, "reproject_view: from", from)) return rc;
+    if (int rc = check_ray_camera(c, "reproject_view: to", to)) return rc;
+    int rc;
+    if ((rc = reproject_begin(c))) return rc;
+    if ((rc = c->rp_rays.reserve(c, (size_t)c->width * c->height * 32))) return rc;
+    // Ray-made guide images carry no camera: the current ones cannot be known to be `from`'s, so both views' are rendered
+    if ((rc = reproject_view_guides(c, *from))) return rc;
+    if ((rc = reproject_keep_history(c))) return rc;
+    if ((rc = reproject_view_guides(c, *to))) return rc;
+    return reproject_run(c, p, from->model, from->camera, from->fov_deg, out);
 }
 
 // The image a display source names, or NULL with the error set (`what` names the caller).

@@ -77,7 +77,8 @@ class CameraController:
 class InteractiveSession:
     """main.cpp:573-630 without the window: one ``frame()`` per loop iteration."""
 
-    _model = _guide_rays = _guide_view = None        # (class defaults: no camera model, guides keyed by the camera)
+    _model = _guide_rays = _guide_view = _rendered_view = None   # (class defaults: no camera model, guides keyed by the camera)
+    _counts_differ = False                           # reproject_view left pixels with different frame counts
 
     def __init__(self, tracer, width: int, height: int, camera: CameraController, max_bounce_depth: int = 4):
         self.pt = tracer
@@ -86,6 +87,7 @@ class InteractiveSession:
         self.max_bounce_depth = max_bounce_depth
         self.frame_count = 0
         self._rendered_camera = None                 # uniforms of the last call that rendered (reproject's `from`)
+        self._rendered_view = None                   # ... and its view: (uniforms, model, fov_deg) (reproject_view's `from`)
         self._lens = None                            # set_lens: (aa_width, lens_radius, focus_distance)
         self._model = None                           # set_camera_model: (model, fov_deg, per_pixel)
         self._rays = None                            # the ray buffer of the last frame (alive while its call runs)
@@ -116,7 +118,8 @@ class InteractiveSession:
         ``PathTracer.render_rays``; ``preview()`` takes its guide images from the model's
         un-jittered rays (the pinhole model keeps ``render_guides``), made again whenever the
         camera, the model or ``fov_deg`` has changed since; ``reproject()`` is refused under
-        another model than pinhole.  A redraw stays the reference's depth-1 frame 0 of the pinhole camera when the
+        another model than pinhole (``reproject_view()`` works under every model and across a
+        change of model).  A redraw stays the reference's depth-1 frame 0 of the pinhole camera when the
         model is pinhole, and is the same frame through the ray path otherwise.  Never
         called, nothing changes."""
         from . import _native as N_
@@ -126,6 +129,16 @@ class InteractiveSession:
         if name != "pinhole" and self._lens is not None and self._lens[1] > 0:
             raise ValueError("set_camera_model: a lens (set_lens) needs the pinhole model")
         self._model = (name, float(fov_deg), int(bool(per_pixel)))
+
+    def _view(self, cam):
+        """(uniforms, model, fov_deg): the view the still frames render with camera uniforms ``cam``."""
+        name, fov, _ = self._model if self._model is not None else ("pinhole", 180.0, 0)
+        return (cam, name, fov)
+
+    def _remember(self, cam):
+        """A call rendered (or reprojected into) the view of ``cam``: what the next reprojection starts from."""
+        self._rendered_camera = cam
+        self._rendered_view = self._view(cam)
 
     def _model_rays(self, cam, n: int, jitter: bool = True):
         """(rays, frame_stride) of frames frame_count .. + n - 1 for the camera model (none set: the pinhole model's)."""
@@ -165,6 +178,7 @@ class InteractiveSession:
         if redraw:                                   # main.cpp:592-596
             depth = 1
             self.frame_count = 0
+            self._counts_differ = False              # the image starts again: every pixel at one count
         else:                                        # main.cpp:597-601
             depth = self.max_bounce_depth
         cam = self.camera.uniforms()
@@ -176,7 +190,7 @@ class InteractiveSession:
             self.pt.render_cameras(self.frame_count, self._lens_cameras(cam, 1), band, n_shards, shard)
         else:
             self.pt.render(self.frame_count, 1, band, n_shards, shard)   # main.cpp:612-613
-        self._rendered_camera = cam
+        self._remember(cam)
         if not redraw:                               # main.cpp:628
             self.frame_count += 1
         return depth, self.frame_count
@@ -227,7 +241,7 @@ class InteractiveSession:
                 stats = self.pt.render_adaptive(self.frame_count, n, threshold, min_frames)
             if stats["n_active_pixels"] == 0:        # nothing was rendered: the frames were not issued
                 break
-            self._rendered_camera = cam
+            self._remember(cam)
             self.frame_count += n
             done += n
         return stats, done
@@ -242,14 +256,45 @@ class InteractiveSession:
         accumulation was last reset (``frame_counted``, ``render_until`` and
         ``render_adaptive_until`` enable them).  Returns the call's statistics."""
         if self._model is not None and self._model[0] != "pinhole":
-            raise ValueError(f"reproject: the {self._model[0]!r} camera model has no reprojection (pinhole views only)")
+            raise ValueError(f"reproject: the {self._model[0]!r} camera model has no reprojection (pinhole views only): "
+                             "reproject_view() takes every model")
         if self.frame_count == 0 or self._rendered_camera is None:
             raise ValueError("reproject: nothing was rendered yet (frame_count == 0)")
         cam = self.camera.uniforms()
         self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
         stats = self.pt.reproject(self._rendered_camera, **params)
         self._guide_view = None                      # it left camera-keyed guides of the new view
-        self._rendered_camera = cam
+        self._remember(cam)
+        return stats
+
+    def reproject_view(self, **params) -> dict:
+        """``reproject()`` under any camera model (``set_camera_model``) and across a change
+        of model or ``fov_deg`` -- a switch from pinhole to fisheye keeps the image: carry
+        the accumulation and the sample moments over from the view of the last call that
+        rendered (its uniforms, model and ``fov_deg``) into the view the still frames render
+        now (``PathTracer.reproject_view``, whose ``params`` these are).  Sets the frame at
+        the full bounce depth, keeps ``frame_count`` and remembers the new view, so moves
+        chain.  Two pinhole views are ``reproject()``.  The call leaves the guide images of
+        the new view: ``preview()`` does not render them again.  Continue with
+        ``frame_counted()``.  Returns the call's statistics."""
+        if self.frame_count == 0 or self._rendered_view is None:
+            raise ValueError("reproject_view: nothing was rendered yet (frame_count == 0)")
+        cam = self.camera.uniforms()
+        (cam_a, model_a, fov_a), (_, model_b, fov_b) = self._rendered_view, self._view(cam)
+        if model_a == "pinhole" and model_b == "pinhole":
+            return self.reproject(**params)
+        self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
+        stats = self.pt.reproject_view((model_a, cam_a, fov_a), (model_b, cam, fov_b), **params)
+        self._counts_differ = True                   # frame_counted() continues at every pixel's own count
+        self._guide_rays = None                      # (the library made the new view's guides from rays of its own)
+        if model_b != "pinhole":
+            self._guide_view = self._guide_want()
+        else:
+            # Ray-made guides are accepted for any camera, and under the pinhole model the session relies on the
+            # library's own staleness check, which they would defeat: camera-keyed ones instead
+            self.pt.render_guides()
+            self._guide_view = None
+        self._remember(cam)
         return stats
 
     def frame_counted(self, n: int = 1) -> dict:
@@ -261,10 +306,19 @@ class InteractiveSession:
         the sequence, blended at the weight of that frame number (the statistics then
         report every pixel active and the call's batch plan).  The per-pixel-count form
         of those frames is ``PathTracer.render_rays_adaptive`` with ``threshold 0,
-        min_frames 0xFFFFFFFF``."""
+        min_frames 0xFFFFFFFF``: after ``reproject_view()`` -- until the next redraw -- the
+        frames of a camera model or a lens go through it, so that a disoccluded pixel
+        takes the next frame whole."""
         self.pt.enable_moments(True)
         cam = self.camera.uniforms()
         self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
+        if self._counts_differ and (self._model is not None or self._lens is not None):
+            # after reproject_view the pixels hold different counts: the frames' rays at every pixel's own weight
+            rays, stride = self._model_rays(cam, n)
+            stats = self.pt.render_rays_adaptive(self.frame_count, n, rays, stride, 0.0, 0xFFFFFFFF)
+            self._remember(cam)
+            self.frame_count += n
+            return stats
         if self._model is not None or self._lens is not None:
             if self._model is not None:
                 rays, stride = self._model_rays(cam, n)
@@ -273,12 +327,12 @@ class InteractiveSession:
                 self.pt.render_cameras(self.frame_count, self._lens_cameras(cam, n))
             plan = self.pt.cameras_batch_plan(n)
             npix, ntiles = self.width * self.height, ((self.width + 7) // 8) * ((self.height + 7) // 8)
-            self._rendered_camera = cam
+            self._remember(cam)
             self.frame_count += n
             return {"n_pixels": npix, "n_active_pixels": npix, "n_tiles": ntiles, "n_active_tiles": ntiles,
                     "frames_per_batch": plan["frames_per_batch"], "n_batches": plan["n_batches"]}
         stats = self.pt.render_adaptive(self.frame_count, n, 0.0, 0xFFFFFFFF)
-        self._rendered_camera = cam
+        self._remember(cam)
         self.frame_count += n
         return stats
 

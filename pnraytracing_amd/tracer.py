@@ -536,17 +536,39 @@ class PathTracer:
         cam = N.Camera()
         c = np.asarray(from_camera, np.float32).reshape(4, 3)
         cam.eye[:], cam.lower_left[:], cam.horizontal[:], cam.vertical[:] = (list(map(float, r)) for r in c)
-        given = (normal_min, position_tolerance, max_history)
-        if all(v is None for v in given):
-            params = None
-        else:
-            if max_history is not None and not 0 <= max_history <= 0xFFFFFFFF:
-                raise ValueError(f"reproject: max_history = {max_history} is outside 0 .. 2**32 - 1")
-            d = REPROJECT_DEFAULTS
-            p = N.ReprojectParams(*(d[k] if v is None else v for k, v in zip(d, given)), 0)
-            params = ctypes.byref(p)
+        params = self._reproject_params("reproject", normal_min, position_tolerance, max_history)
         st = N.ReprojectStats()
         self._ck(self._lib.pnrt_reproject(self._ctx, ctypes.byref(cam), params, ctypes.byref(st)), "pnrt_reproject")
+        return {f: getattr(st, f) for f, _ in st._fields_ if f != "reserved"}
+
+    @staticmethod
+    def _reproject_params(who, normal_min, position_tolerance, max_history):
+        """``pnrt_reproject_params`` by reference, or None (the library's defaults) when nothing was given."""
+        given = (normal_min, position_tolerance, max_history)
+        if all(v is None for v in given):
+            return None
+        if max_history is not None and not 0 <= max_history <= 0xFFFFFFFF:
+            raise ValueError(f"{who}: max_history = {max_history} is outside 0 .. 2**32 - 1")
+        d = REPROJECT_DEFAULTS
+        return ctypes.byref(N.ReprojectParams(*(d[k] if v is None else v for k, v in zip(d, given)), 0))
+
+    def reproject_view(self, from_view, to_view, normal_min: float | None = None, position_tolerance: float | None = None,
+                       max_history: int | None = None) -> dict:
+        """``reproject`` with both views given as camera models (pnrt_reproject_view;
+        synchronous, whole image): from the view ``from_view`` the accumulation was rendered
+        with into ``to_view``, each a ``RayCamera`` (``ray_camera``) or a ``(model, camera,
+        fov_deg)`` tuple -- the model's centre rays; jitter and lens fields are checked and
+        ignored.  The ``set_frame`` camera is not read.  An equirectangular ``from_view``
+        wraps in x; a pixel of ``to_view`` without a ray counts as missed.  Continue with
+        ``render_rays_adaptive(first, n, rays, stride, 0.0, 0xFFFFFFFF)``.  Leaves the guide
+        images of ``to_view``'s centre rays (``make_rays`` + ``render_guides_rays``).
+        Arguments left out take the library's defaults.  Returns the fields of
+        ``pnrt_reproject_stats``."""
+        views = [v if isinstance(v, N.RayCamera) else self.ray_camera(*v) for v in (from_view, to_view)]
+        params = self._reproject_params("reproject_view", normal_min, position_tolerance, max_history)
+        st = N.ReprojectStats()
+        self._ck(self._lib.pnrt_reproject_view(self._ctx, ctypes.byref(views[0]), ctypes.byref(views[1]), params, ctypes.byref(st)),
+                 "pnrt_reproject_view")
         return {f: getattr(st, f) for f, _ in st._fields_ if f != "reserved"}
 
     def pack_rows(self, dst_ptr: int, band: int, n_shards: int, shard: int):

@@ -17,7 +17,17 @@ profiles/reproject/).  Reported, not asserted.
            preview_variance() on top of it, and the shares reprojected / disoccluded /
            missed.
 
-usage: python tools/reproject_measure.py cost|quality [out.json]"""
+  cost_view     pnrt_reproject_view (results in profiles/reproject_view/):
+           the same drag steps with both views one camera model, per model: the call's wall
+           time, the PNRT_K_PRIMARY sum (two guide traces) and the PNRT_K_BLEND sum (two
+           pnrt_make_rays launches, the kernel, the four copies); pnrt_make_rays timed alone
+           the same way, so the kernel's time is the blend sum less the copies and two of
+           those.  Beside it pnrt_reproject in the same process.
+  quality_view  the quality experiment under the 180-degree fisheye: reproject_view() +
+           frame_counted(K) against a redraw + K frames, against a 1024-frame render of
+           the new view's rays.
+
+usage: python tools/reproject_measure.py cost|quality|cost_view|quality_view [out.json]"""
 import ctypes
 import json
 import os
@@ -215,6 +225,103 @@ def quality(w=512, h=512, frames_a=64, ks=(1, 4, 16), long_frames=1024):
     return res
 
 
+# ---- pnrt_reproject_view ---------------------------------------------------------
+VIEW_FOV = 180.0                 # the fisheye's
+
+
+def cost_view_at(w, h, reps=5):
+    from pnraytracing_amd import _native as N
+    cfg = scenes.bunny_c2(width=w, height=h, spp=1)
+    cam = controller(w, h)
+    res = {"size": f"{w}x{h}", "models": {}}
+    med = statistics.median
+    with PathTracer(0) as pt:
+        pt.load(cfg)
+        pt.enable_moments()
+        res["copies_alone_ms"] = med(copies_alone_ms(pt.stream_handle(), w * h * 16, reps))
+        for model in N.CAM_MODELS + ("pnrt_reproject",):
+            runs, rays_ms = [], []
+            for rep in range(reps + 1):              # the first call allocates: left out
+                cam_a = cam.uniforms()
+                assert cam.rotate(*drag(rep))
+                cam_b = cam.uniforms()
+                pt.set_frame(w, h, cam_a, cfg.max_depth)
+                pt.render(0, 8)
+                pt.synchronize()
+                pt.profile_enable(True)
+                t0 = time.perf_counter()
+                if model == "pnrt_reproject":        # the call lent nothing: A's guides rendered by the call
+                    pt.set_frame(w, h, cam_b, cfg.max_depth)
+                    t0 = time.perf_counter()
+                    st = pt.reproject(cam_a)
+                else:
+                    st = pt.reproject_view((model, cam_a, VIEW_FOV), (model, cam_b, VIEW_FOV))
+                wall = (time.perf_counter() - t0) * 1e3
+                prof = pt.profile_read()
+                pt.profile_enable(False)
+                runs.append({"wall_ms": wall, "primary_ms": prof["primary"][0], "primary_launches": prof["primary"][1],
+                             "blend_ms": prof["blend"][0], "blend_launches": prof["blend"][1]})
+                if model != "pnrt_reproject":
+                    pt.profile_enable(True)
+                    keep = pt.make_rays(model, cam_b, 0, 1, fov_deg=VIEW_FOV)
+                    rays_ms.append(pt.profile_read()["blend"][0])
+                    pt.profile_enable(False)
+                    del keep
+            row = {k: med(r[k] for r in runs[1:]) for k in ("wall_ms", "primary_ms", "blend_ms")}
+            row["wall_ms_spread"] = [min(r["wall_ms"] for r in runs[1:]), max(r["wall_ms"] for r in runs[1:])]
+            row["blend_launches"], row["primary_launches"] = runs[-1]["blend_launches"], runs[-1]["primary_launches"]
+            row["make_rays_alone_ms"] = med(rays_ms[1:]) if rays_ms else 0.0
+            row["kernel_ms"] = row["blend_ms"] - res["copies_alone_ms"] - 2 * row["make_rays_alone_ms"]
+            row["runs"] = runs
+            row["stats"] = st
+            res["models"][model] = row
+    return res
+
+
+def quality_view(w=512, h=512, frames_a=64, ks=(1, 4, 16), long_frames=1024, model="fisheye", fov=VIEW_FOV):
+    cfg = scenes.bunny_c2(width=w, height=h, spp=1)
+    res = {"size": f"{w}x{h}", "model": model, "fov_deg": fov, "frames_at_A": frames_a, "reference_frames": long_frames, "K": {}}
+    with PathTracer(0) as pt:
+        pt.load(cfg)
+        moved = controller(w, h)
+        assert moved.rotate(*DRAG)
+        pt.set_frame(w, h, moved.uniforms(), cfg.max_depth)
+        rays = pt.make_rays(model, moved.uniforms(), 0, 1, fov_deg=fov)
+        pt.render_rays(0, long_frames, rays, 0)
+        ref = lum(pt.read_accum())
+        res["ref_mean_lum"] = float(ref.mean())
+
+        def rmse(img):
+            return float(np.sqrt(np.mean((lum(img) - ref) ** 2)))
+
+        def session():
+            pt.reset_accum()
+            s = InteractiveSession(pt, w, h, controller(w, h), cfg.max_depth)
+            s.set_camera_model(model, fov_deg=fov)
+            s.frame_counted(frames_a)
+            s.camera = moved
+            return s
+
+        for k in ks:
+            row = {}
+            s = session()                            # (a) redraw, then K frames
+            s.frame(redraw=True)
+            pt.enable_moments(True)
+            for _ in range(k):
+                s.frame()
+            row["redraw"] = {"raw": rmse(pt.read_accum())}
+            s = session()                            # (b) reproject_view, then K frames at every pixel's own weight
+            st = s.reproject_view()
+            s.frame_counted(k)
+            row["reproject_view"] = {"raw": rmse(pt.read_accum())}
+            row["stats"] = st
+            res["K"][str(k)] = row
+            print(k, json.dumps(row), flush=True)
+        n = st["n_pixels"]
+        res["shares"] = {x: st["n_" + x] / n for x in ("reprojected", "disoccluded", "missed")}
+    return res
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else ""
     if what == "cost":
@@ -223,6 +330,14 @@ if __name__ == "__main__":
             print(c["size"], json.dumps({k: c[k] for k in ("guides_current", "guides_rendered_by_the_call", "summary", "bytes", "stats")}))
     elif what == "quality":
         out = {"quality": quality()}
+    elif what == "cost_view":
+        out = {"cost_view": [cost_view_at(1920, 1080), cost_view_at(512, 512)]}
+        for c in out["cost_view"]:
+            print(c["size"], "copies alone", c["copies_alone_ms"])
+            for m, row in c["models"].items():
+                print(" ", m, json.dumps({k: v for k, v in row.items() if k != "runs"}))
+    elif what == "quality_view":
+        out = {"quality_view": quality_view()}
     else:
         sys.exit(__doc__)
     if len(sys.argv) > 2:
