@@ -158,6 +158,64 @@ int pnrt_update_vertices(pnrt_ctx* ctx, int first, int count, const float* verti
 int pnrt_update_vertices_device(pnrt_ctx* ctx, int first, int count, const void* vertices15_dev,
                                 const float* lights, float lights_sum_area);
 
+/* Models moved on the device by a matrix.  Not in the reference, which places
+ * every model once at load (main.cpp:207-237, ModelOutput model.hpp:101-135):
+ * this is that step, on the device, in front of pnrt_update_vertices's refit,
+ * so that moving a model costs its matrix and not its vertices.
+ *
+ * pnrt_define_model keeps a device copy (32 bytes a vertex) of the MODEL-space
+ * records of vertices first_vertex .. first_vertex + count - 1, 8 floats each:
+ * position 3, normal 3, texcoord 2 (the device keeps no tangent or bitangent).
+ * It changes nothing in the scene and returns ids 0, 1, 2, ... in definition
+ * order.  Errors, each with nothing kept: PNRT_E_STATE before
+ * pnrt_upload_scene; PNRT_E_ARG for count < 1, a range outside the uploaded
+ * vertex array or overlapping an already defined model's, a NULL pointer, or
+ * (the _device form, which reads device memory of the context's device) a
+ * pointer that is not 4-byte aligned.  pnrt_upload_scene forgets every model
+ * and frees the copies: the ids are invalid afterwards.
+ *
+ * pnrt_place_models writes, for each of the n placements (1 .. 1024), the
+ * world-space records of that model's range, then refits once as
+ * pnrt_update_vertices does: synchronous, it waits for the calls in flight,
+ * and the guide images and kept primary records go stale.  With
+ * N = transpose(inverse(M)) in glm's expression order (libpnrt_host.so's
+ * pnrt_normal_matrix), every product and sum rounded on its own, for row r:
+ *   pos[r]    = (M[0][r] * p.x + M[1][r] * p.y) + (M[2][r] * p.z + M[3][r] * 1.0f)
+ *   normal[r] = (N[0][r] * n.x + N[1][r] * n.y) + (N[2][r] * n.z + N[3][r] * 1.0f)
+ * and the texcoords copied: the bits of libpnrt_host.so's pnrt_scene_add_mesh.
+ * The normal is not normalised (ModelOutput does not).  The result is defined
+ * from the model-space copy, never from the current records: placing M1 then
+ * M2 gives the bits of placing M2 alone.  A later pnrt_update_vertices on a
+ * model's range is legal; the model's next placement overwrites it.
+ *
+ * relight = 0 keeps the prefix areas and lights_sum_area, as lights == NULL
+ * does in pnrt_update_vertices.  relight = 1 recomputes them from the new
+ * positions: area = (float)((double)length(cross(p1 - p0, p2 - p0)) * 0.5) per
+ * light triangle and the float prefix of main.cpp:374-383, which is
+ * libpnrt_host.so's pnrt_scene_relight.  This replaces EVERY entry's area, those
+ * of untouched lights included: a caller with areas of its own follows with
+ * pnrt_update_vertices(ctx, 0, 0, NULL, lights, lights_sum_area).
+ *
+ * Errors, with nothing changed: PNRT_E_STATE before pnrt_upload_scene;
+ * PNRT_E_ARG for n outside 1 .. 1024, NULL placements, relight not 0 or 1,
+ * and -- the message names the placement -- an unknown id, an id named twice,
+ * reserved != 0, a matrix float that is not finite, or a matrix whose N has a
+ * non-finite entry (a singular one); PNRT_E_TRACE as pnrt_read_accum returns it. */
+typedef struct {
+    int model;                /* pnrt_define_model's id */
+    float matrix[16];         /* column major, as libpnrt_host.so's pnrt_model_matrix writes it */
+    int reserved;             /* 0 */
+} pnrt_placement;             /* 72 bytes */
+int pnrt_define_model(pnrt_ctx* ctx, int first_vertex, int count, const float* model8, int* model_id_out);
+int pnrt_define_model_device(pnrt_ctx* ctx, int first_vertex, int count, const void* model8_dev, int* model_id_out);
+int pnrt_place_models(pnrt_ctx* ctx, const pnrt_placement* placements, int n, int relight);
+
+/* The vertex records the device currently holds, 8 floats each (position 3,
+ * normal 3, texcoord 2), first .. first + count - 1, to the host.  Synchronous.
+ * PNRT_E_STATE before pnrt_upload_scene; PNRT_E_ARG for a range outside the
+ * uploaded array. */
+int pnrt_read_vertices(pnrt_ctx* ctx, int first, int count, float* out8);
+
 /* The boxes the device currently holds, into floats 0-5 of every node of the
  * caller's pre-order node array (main.cpp:488-501 layout); floats 6-11 are
  * read, not written.  Not in the reference.  The array must be the topology

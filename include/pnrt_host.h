@@ -49,6 +49,10 @@ typedef struct { int kind; float angle_deg; float v[3]; } pnrt_xform;
 const char* pnrt_host_last_error(void);
 
 int pnrt_model_matrix(const pnrt_xform* ops, int n_ops, float out_col_major[16]);
+/* transpose(inverse(m)) in glm's compute_inverse expression order, column major: the
+ * matrix ModelOutput (model.hpp:101-135) takes a model's normals through, and the N of
+ * libpnrt.so's pnrt_place_models.  A singular m gives non-finite entries. */
+int pnrt_normal_matrix(const float m_col_major[16], float out_col_major[16]);
 
 pnrt_scene* pnrt_scene_create(void);
 void pnrt_scene_destroy(pnrt_scene* s);

@@ -177,6 +177,11 @@ class RayCamera(ctypes.Structure):
                 ("reserved", ctypes.c_int)]
 
 
+class Placement(ctypes.Structure):
+    """``pnrt_placement`` (72 bytes)."""
+    _fields_ = [("model", ctypes.c_int), ("matrix", ctypes.c_float * 16), ("reserved", ctypes.c_int)]
+
+
 QUERY_CLOSEST, QUERY_ANY = 0, 1                # PNRT_QUERY_*
 
 
@@ -194,6 +199,7 @@ def _sig(lib, name, res, *args):
 def _type_host(lib):
     _sig(lib, "pnrt_host_last_error", ctypes.c_char_p)
     _sig(lib, "pnrt_model_matrix", INT, ctypes.POINTER(Xform), INT, F)
+    _sig(lib, "pnrt_normal_matrix", INT, F, F)
     _sig(lib, "pnrt_scene_create", P)
     _sig(lib, "pnrt_scene_destroy", None, P)
     _sig(lib, "pnrt_scene_add_material", INT, P, F)
@@ -230,6 +236,10 @@ def _type_device(lib):
     _sig(lib, "pnrt_update_vertices", INT, P, INT, INT, F, F, ctypes.c_float)
     _sig(lib, "pnrt_update_vertices_device", INT, P, INT, INT, P, F, ctypes.c_float)
     _sig(lib, "pnrt_read_bvh_boxes", INT, P, F, INT)
+    _sig(lib, "pnrt_define_model", INT, P, INT, INT, F, PINT)
+    _sig(lib, "pnrt_define_model_device", INT, P, INT, INT, P, PINT)
+    _sig(lib, "pnrt_place_models", INT, P, ctypes.POINTER(Placement), INT, INT)
+    _sig(lib, "pnrt_read_vertices", INT, P, INT, INT, F)
     _sig(lib, "pnrt_upload_env", INT, P, F, F, INT, INT)
     _sig(lib, "pnrt_set_frame", INT, P, INT, INT, ctypes.POINTER(Camera), INT)
     _sig(lib, "pnrt_set_options", INT, P, INT)

@@ -1,6 +1,6 @@
 """In-tree build of the native libraries (no JIT cache, nothing installed).
 
-    libpnrt_host.so  g++   csrc/host/pnrt_host.cpp          (host scene library)
+    libpnrt_host.so  g++   csrc/host/pnrt_host.cpp, csrc/pn_glm.h   (host scene library)
     libpnrt.so       hipcc csrc/pnrt_device.hip, gfx950     (device library)
     oracle/liboracle.so    gcc (TEST-ONLY parity oracle; see oracle/)
     oracle/_ref/ref_driver g++ on /root/reference headers (only where present)
@@ -30,7 +30,7 @@ DEVICE_SRCS = ["pnrt_device.hip"]
 DEVICE_DEPS = ["pnrt_device.hip", "pt_diag.h", "pt_common.h", "pt_kernel.h", "pt_shade.h", "pt_path.h", "pt_passes.h", "pt_wf.h",
                "pt_env.h", "pt_bvh.h", "pt_guides.h", "pt_denoise.h", "pt_moments.h", "pt_adaptive.h", "pt_query.h", "pn_math.h",
                "sobol_v.inc", "pt_denoise_var.h", "pt_reproject.h", "pt_display.h", "pt_refit.h", "pt_cameras.h", "pt_rays.h",
-               "pt_reproject_view.h"]
+               "pt_reproject_view.h", "pt_place.h", "pn_glm.h"]
 
 
 def _run(cmd, cwd=None):
@@ -48,7 +48,7 @@ def _stale(target, deps):
 def build_host(force=False):
     out = os.path.join(PKG, "libpnrt_host.so")
     src = os.path.join(CSRC, "host", "pnrt_host.cpp")
-    if force or _stale(out, [src, os.path.join(INC, "pnrt_host.h")]):
+    if force or _stale(out, [src, os.path.join(CSRC, "pn_glm.h"), os.path.join(INC, "pnrt_host.h")]):
         _run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
               "-Wall", "-I", INC, src, "-o", out])
     return out
@@ -142,6 +142,8 @@ ABI_CALLERS = {
     "c_abi_rays.c": ["-lamdhip64"],
     # pnrt_render_rays(0, 4), then pnrt_render_rays_adaptive over fisheye sets (tests/test_gpu_rays_adaptive_c_abi.py)
     "c_abi_rays_adaptive.c": ["-lamdhip64"],
+    # a model defined and placed by a matrix: pnrt_define_model, pnrt_place_models, pnrt_read_vertices (tests/test_gpu_place_c_abi.py)
+    "c_abi_place.c": [],
 }
 
 
@@ -174,7 +176,7 @@ def build_abi_caller(force=False):
             os.path.join(PKG, "libpnrt.so"), os.path.join(PKG, "libpnrt_host.so")]
     if not all(os.path.exists(d) for d in need):
         return None
-    outs = [_abi_caller(source, force) for source in ABI_CALLERS if source not in ("c_abi_refit.c", "c_abi_cameras.c", "c_abi_rays.c", "c_abi_rays_adaptive.c")]
+    outs = [_abi_caller(source, force) for source in ABI_CALLERS if source not in ("c_abi_refit.c", "c_abi_cameras.c", "c_abi_rays.c", "c_abi_rays_adaptive.c", "c_abi_place.c")]
     return outs[0]
 
 
@@ -194,6 +196,10 @@ def build_rays_adaptive_abi_caller(force=False):
     return _abi_caller("c_abi_rays_adaptive.c", force)
 
 
+def build_place_abi_caller(force=False):
+    return _abi_caller("c_abi_place.c", force)
+
+
 def build_oracle(force=False):
     odir = os.path.join(REPO, "oracle")
     _run(["make", "-s", "-C", odir] + (["-B"] if force else []))
@@ -211,6 +217,7 @@ def build_all(force=False):
     build_cameras_abi_caller(force)
     build_rays_abi_caller(force)
     build_rays_adaptive_abi_caller(force)
+    build_place_abi_caller(force)
     build_oracle(force)
 
 

@@ -30,6 +30,8 @@
 #include "pt_reproject_view.h"
 #include "pt_display.h"
 #include "pt_refit.h"
+#include "pt_place.h"
+#include "pn_glm.h"
 #include "pt_cameras.h"
 #include "pt_rays.h"
 
@@ -275,6 +277,14 @@ struct pnrt_ctx {
     // in-place geometry edits (pnrt_update_vertices; pt_refit.h): none until the first call
     DevBuf<float> rf_stage;                // the host form's staging buffer: vertex records in
     DevBuf<RefitResult> rf_res;            // the root box and the non-finite flag the host reads back
+    // models placed by a matrix (pnrt_define_model, pnrt_place_models; pt_place.h): none until the first
+    // definition; forgotten, their copies freed, with the scene
+    struct PlaceModel {
+        int first = 0, count = 0;          // the model's vertex range
+        DevBuf<float4> rec;                // its model-space records, two float4 per vertex
+    };
+    std::vector<PlaceModel> models;        // the index is the model's id
+    DevBuf<PlaceEntry> pl_table;           // a call's placement table, PLACE_MAX entries
     // per-frame cameras (pnrt_render_cameras; pt_cameras.h): none until the first call.  A call's array is
     // copied into a pinned staging block, from which each batch's table is copied to its pipe in stream
     // order; a block is reused once the event behind its call's last copy has completed
@@ -376,6 +386,7 @@ static int prof_collect(pnrt_ctx* c) {
 
 static void free_scene(pnrt_ctx* c) {
     c->scene_allocs.clear();
+    c->models.clear();
     c->has_scene = false;
 }
 
@@ -1688,6 +1699,46 @@ int pnrt_update_materials(pnrt_ctx* c, int first, int count, const float* rec) {
 #define REFIT_MAX_STAGE (1 << 20)    // vertex records per staged copy of the host form (60 MB)
 #endif
 
+// The tail of every edit of `verts` (pnrt_update_vertices, pnrt_place_models), queued behind the writes
+// on the context's stream: every per-triangle record regathered, the light records, the leaves, the
+// levels, the root box and the non-finite flag, the host copy of the light records -- then the scene
+// is another one.  c->rf_res is reserved by the caller, before it changes anything.
+static int refit_tail(pnrt_ctx* c) {
+    DevScene& s = c->scene;
+    hipStream_t st = c->stream;
+    const int nl = s.n_lights;
+    float4* nodes = const_cast<float4*>(s.nodes);
+    RefitResult res0{};
+    for (int k = 0; k < 3; ++k) { res0.root[k] = s.root_min[k]; res0.root[3 + k] = s.root_max[k]; }
+    HIPCHK(c, hipMemcpyAsync(c->rf_res, &res0, sizeof res0, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pt_refit_gather_kernel, dim3((s.n_tris + 255) / 256), dim3(256), 0, st, s.tri_idx, s.verts,
+                       const_cast<float4*>(s.tris), const_cast<float4*>(s.tri_attr), s.n_tris, s.n_verts);
+    hipLaunchKernelGGL(pt_refit_lights_kernel, dim3((nl + 1 + 255) / 256), dim3(256), 0, st, s.lights, s.tri_idx, s.verts,
+                       const_cast<float4*>(s.light_rec), nl, s.n_tris, s.n_verts);
+    const int nn = s.n_nodes;
+    hipLaunchKernelGGL(pt_refit_leaves_kernel, dim3(nn ? (2 * (unsigned)nn + 255) / 256 : 1), dim3(256), 0, st, nodes, nn,
+                       s.tris, s.n_tris, s.leaf_table, s.n_leaf_table, s.has_leaf_table, s.root_ref, c->rf_res);
+    // the deepest level has leaf children only; level 0 is the root's launch
+    const int levels = (int)c->level_off.size() - 1;
+    for (int d = levels - 2; d >= 1; --d) {
+        const int lo = c->level_off[d], hi = c->level_off[d + 1];
+        hipLaunchKernelGGL(pt_refit_level_kernel, dim3((2 * (unsigned)(hi - lo) + 255) / 256), dim3(256), 0, st, nodes, nn, lo,
+                           hi, 0, c->rf_res);
+    }
+    if (nn > 0) hipLaunchKernelGGL(pt_refit_level_kernel, dim3(1), dim3(64), 0, st, nodes, nn, 0, 1, 1, c->rf_res);
+    HIPCHK(c, hipGetLastError());
+    RefitResult res{};
+    HIPCHK(c, hipMemcpyAsync(&res, c->rf_res, sizeof res, hipMemcpyDeviceToHost, st));
+    // pnrt_update_materials patches the host copy of the light records and uploads spans of it
+    HIPCHK(c, hipMemcpyAsync(c->light_rec_host.data(), s.light_rec, c->light_rec_host.size() * sizeof(float4),
+                             hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (int k = 0; k < 3; ++k) { s.root_min[k] = res.root[k]; s.root_max[k] = res.root[3 + k]; }
+    c->boxes_finite = res.nonfinite == 0;
+    ++c->scene_epoch;                    // primary records, guide images: traced through the old geometry
+    return PNRT_OK;
+}
+
 // pnrt_update_vertices / _device: `src_host` or `src_dev` holds the records (pt_refit.h)
 static int update_vertices(pnrt_ctx* c, const char* who, int first, int count, const float* src_host, const float* src_dev,
                            const float* Lt, float lsum) {
@@ -1719,11 +1770,7 @@ static int update_vertices(pnrt_ctx* c, const char* who, int first, int count, c
         if ((rc = c->rf_res.reserve(c, sizeof(RefitResult)))) return rc;
         if (src_host && (rc = c->rf_stage.reserve(c, (size_t)std::min(count, REFIT_MAX_STAGE) * 60))) return rc;
         hipStream_t st = c->stream;
-        RefitResult res0{};
-        for (int k = 0; k < 3; ++k) { res0.root[k] = s.root_min[k]; res0.root[3 + k] = s.root_max[k]; }
-        HIPCHK(c, hipMemcpyAsync(c->rf_res, &res0, sizeof res0, hipMemcpyHostToDevice, st));
         float4* verts = const_cast<float4*>(s.verts);
-        float4* nodes = const_cast<float4*>(s.nodes);
         if (src_dev)
             hipLaunchKernelGGL(pt_refit_scatter_kernel, dim3((count + 255) / 256), dim3(256), 0, st, src_dev, verts, first, count,
                                s.n_verts);
@@ -1736,36 +1783,12 @@ static int update_vertices(pnrt_ctx* c, const char* who, int first, int count, c
                                    s.n_verts);
                 HIPCHK(c, hipStreamSynchronize(st));
             }
-        hipLaunchKernelGGL(pt_refit_gather_kernel, dim3((s.n_tris + 255) / 256), dim3(256), 0, st, s.tri_idx, s.verts,
-                           const_cast<float4*>(s.tris), const_cast<float4*>(s.tri_attr), s.n_tris, s.n_verts);
-        hipLaunchKernelGGL(pt_refit_lights_kernel, dim3((nl + 1 + 255) / 256), dim3(256), 0, st, s.lights, s.tri_idx, s.verts,
-                           const_cast<float4*>(s.light_rec), nl, s.n_tris, s.n_verts);
-        const int nn = s.n_nodes;
-        hipLaunchKernelGGL(pt_refit_leaves_kernel, dim3(nn ? (2 * (unsigned)nn + 255) / 256 : 1), dim3(256), 0, st, nodes, nn,
-                           s.tris, s.n_tris, s.leaf_table, s.n_leaf_table, s.has_leaf_table, s.root_ref, c->rf_res);
-        // the deepest level has leaf children only; level 0 is the root's launch
-        const int levels = (int)c->level_off.size() - 1;
-        for (int d = levels - 2; d >= 1; --d) {
-            const int lo = c->level_off[d], hi = c->level_off[d + 1];
-            hipLaunchKernelGGL(pt_refit_level_kernel, dim3((2 * (unsigned)(hi - lo) + 255) / 256), dim3(256), 0, st, nodes, nn, lo,
-                               hi, 0, c->rf_res);
-        }
-        if (nn > 0) hipLaunchKernelGGL(pt_refit_level_kernel, dim3(1), dim3(64), 0, st, nodes, nn, 0, 1, 1, c->rf_res);
-        HIPCHK(c, hipGetLastError());
-        RefitResult res{};
-        HIPCHK(c, hipMemcpyAsync(&res, c->rf_res, sizeof res, hipMemcpyDeviceToHost, st));
-        // pnrt_update_materials patches the host copy of the light records and uploads spans of it
-        HIPCHK(c, hipMemcpyAsync(c->light_rec_host.data(), s.light_rec, c->light_rec_host.size() * sizeof(float4),
-                                 hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        for (int k = 0; k < 3; ++k) { s.root_min[k] = res.root[k]; s.root_max[k] = res.root[3 + k]; }
-        c->boxes_finite = res.nonfinite == 0;
-    }
+        if ((rc = refit_tail(c))) return rc;
+    } else ++c->scene_epoch;             // (the areas alone)
     if (Lt) {
         HIPCHK(c, hipMemcpy(const_cast<float2*>(s.lights), lights.data(), lights.size() * sizeof(float2), hipMemcpyHostToDevice));
         set_light_areas(s, lights, nl, lsum);
     }
-    ++c->scene_epoch;                    // primary records, guide images: traced through the old geometry
     return check_fault(c);
 }
 
@@ -1775,6 +1798,117 @@ int pnrt_update_vertices(pnrt_ctx* c, int first, int count, const float* v, cons
 
 int pnrt_update_vertices_device(pnrt_ctx* c, int first, int count, const void* v, const float* lights, float lsum) {
     return update_vertices(c, "update_vertices_device", first, count, nullptr, static_cast<const float*>(v), lights, lsum);
+}
+
+// pnrt_define_model / _device: `src_host` or `src_dev` holds the model-space records (pt_place.h)
+static int define_model(pnrt_ctx* c, const char* who, int first, int count, const float* src_host, const void* src_dev, int* id_out) {
+    if (!c) return PNRT_E_ARG;
+    if (!c->has_scene) return set_err(c, PNRT_E_STATE, std::string(who) + ": upload_scene first");
+    if (count < 1) return set_err(c, PNRT_E_ARG, std::string(who) + ": a model has at least one vertex");
+    if (first < 0 || first > c->scene.n_verts - count)
+        return set_err(c, PNRT_E_ARG, std::string(who) + ": vertex range outside the uploaded array");
+    if (!src_host && !src_dev) return set_err(c, PNRT_E_ARG, std::string(who) + ": records is NULL");
+    if (!id_out) return set_err(c, PNRT_E_ARG, std::string(who) + ": model_id_out is NULL");
+    if ((uintptr_t)src_dev & 3u) return set_err(c, PNRT_E_ARG, std::string(who) + ": records must be 4-byte aligned");
+    for (size_t m = 0; m < c->models.size(); ++m)
+        if (first < c->models[m].first + c->models[m].count && c->models[m].first < first + count)
+            return set_err(c, PNRT_E_ARG, std::string(who) + ": vertices " + std::to_string(first) + " .. " +
+                                              std::to_string(first + count - 1) + " overlap model " + std::to_string(m));
+    HIPCHK(c, hipSetDevice(c->device));
+    pnrt_ctx::PlaceModel m;
+    m.first = first;
+    m.count = count;
+    const size_t bytes = (size_t)count * 32;
+    HIPCHK(c, m.rec.alloc(bytes));
+    HIPCHK(c, hipMemcpyAsync(m.rec, src_host ? (const void*)src_host : src_dev, bytes,
+                             src_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->models.push_back(std::move(m));
+    *id_out = (int)c->models.size() - 1;
+    return PNRT_OK;
+}
+
+int pnrt_define_model(pnrt_ctx* c, int first, int count, const float* model8, int* id_out) {
+    return define_model(c, "define_model", first, count, model8, nullptr, id_out);
+}
+
+int pnrt_define_model_device(pnrt_ctx* c, int first, int count, const void* model8, int* id_out) {
+    return define_model(c, "define_model_device", first, count, nullptr, model8, id_out);
+}
+
+int pnrt_place_models(pnrt_ctx* c, const pnrt_placement* pl, int n, int relight) {
+    if (!c) return PNRT_E_ARG;
+    if (!c->has_scene) return set_err(c, PNRT_E_STATE, "place_models: upload_scene first");
+    if (n < 1 || n > PLACE_MAX) return set_err(c, PNRT_E_ARG, "place_models: 1 .. " + std::to_string(PLACE_MAX) + " placements a call");
+    if (!pl) return set_err(c, PNRT_E_ARG, "place_models: placements is NULL");
+    if (relight != 0 && relight != 1) return set_err(c, PNRT_E_ARG, "place_models: relight is 0 or 1");
+    DevScene& s = c->scene;
+    std::vector<PlaceEntry> table((size_t)n);
+    std::vector<char> placed(c->models.size(), 0);
+    int total = 0;
+    for (int k = 0; k < n; ++k) {
+        const std::string who = "place_models: placement " + std::to_string(k);
+        if (pl[k].reserved != 0) return set_err(c, PNRT_E_ARG, who + ": reserved must be 0");
+        if (pl[k].model < 0 || (size_t)pl[k].model >= c->models.size())
+            return set_err(c, PNRT_E_ARG, who + " names the unknown model " + std::to_string(pl[k].model));
+        if (placed[pl[k].model]) return set_err(c, PNRT_E_ARG, who + " names model " + std::to_string(pl[k].model) + " a second time");
+        placed[pl[k].model] = 1;
+        for (int j = 0; j < 16; ++j)
+            if (!std::isfinite(pl[k].matrix[j])) return set_err(c, PNRT_E_ARG, who + ": matrix float " + std::to_string(j) + " is not finite");
+        const pnglm::mat4 M = pnglm::mat4::load(pl[k].matrix), N = pnglm::normal_matrix(M);
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j)
+                if (!std::isfinite(N.c[i][j])) return set_err(c, PNRT_E_ARG, who + ": the matrix is singular (its normal matrix is not finite)");
+        const pnrt_ctx::PlaceModel& m = c->models[pl[k].model];
+        PlaceEntry& e = table[k];
+        e.prefix = total;
+        e.first = m.first;
+        e.model = m.rec;
+        for (int r = 0; r < 3; ++r) {
+            e.M[r] = make_float4(M.c[0][r], M.c[1][r], M.c[2][r], M.c[3][r]);
+            e.N[r] = make_float4(N.c[0][r], N.c[1][r], N.c[2][r], N.c[3][r]);
+        }
+        total += m.count;                 // (disjoint ranges of one array: at most n_verts)
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // the calls in flight render with the old geometry
+    HIPCHK(c, sync_all(c));
+    int rc;
+    if ((rc = c->rf_res.reserve(c, sizeof(RefitResult))) || (rc = c->pl_table.reserve(c, PLACE_MAX * sizeof(PlaceEntry)))) return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->pl_table, table.data(), table.size() * sizeof(PlaceEntry), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pt_place_kernel, dim3((total + 255) / 256), dim3(256), 0, st, c->pl_table, n, total,
+                       const_cast<float4*>(s.verts), s.n_verts);
+    if ((rc = refit_tail(c))) return rc;
+    if (relight) {
+        // the areas of the light triangles as ModelOutput has them, from the records just read back; the
+        // float prefix of main.cpp:374-383
+        const int nl = s.n_lights;
+        std::vector<float2> lights(nl > WF_LIGHT_SCAN ? nl : WF_LIGHT_SCAN, make_float2(0.f, 0.f));
+        float prefix = 0.f;
+        for (int e = 0; e < nl; ++e) {
+            const float4* r = c->light_rec_host.data() + 7 * (size_t)e;
+            const float area = pnglm::tri_area(pnglm::vec3(r[0].x, r[0].y, r[0].z), pnglm::vec3(r[2].x, r[2].y, r[2].z),
+                                               pnglm::vec3(r[4].x, r[4].y, r[4].z));
+            prefix = e ? area + prefix : area;
+            lights[e] = make_float2((float)c->light_tri[e], prefix);
+        }
+        HIPCHK(c, hipMemcpy(const_cast<float2*>(s.lights), lights.data(), lights.size() * sizeof(float2), hipMemcpyHostToDevice));
+        set_light_areas(s, lights, nl, nl ? prefix : 0.f);
+    }
+    return check_fault(c);
+}
+
+int pnrt_read_vertices(pnrt_ctx* c, int first, int count, float* out8) {
+    if (!c) return PNRT_E_ARG;
+    if (!c->has_scene) return set_err(c, PNRT_E_STATE, "read_vertices: upload_scene first");
+    if (first < 0 || count < 0 || first > c->scene.n_verts - count)
+        return set_err(c, PNRT_E_ARG, "read_vertices: vertex range outside the uploaded array");
+    if (count > 0 && !out8) return set_err(c, PNRT_E_ARG, "read_vertices: out is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sync_all(c));
+    if (count > 0) HIPCHK(c, hipMemcpy(out8, c->scene.verts + 2 * (size_t)first, (size_t)count * 32, hipMemcpyDeviceToHost));
+    return check_fault(c);
 }
 
 int pnrt_read_bvh_boxes(pnrt_ctx* c, float* N, int nn) {

@@ -107,6 +107,29 @@ def model_matrix(ops) -> np.ndarray:
     return out
 
 
+def normal_matrix(m) -> np.ndarray:
+    """transpose(inverse(m)) with glm's float operation order (pnrt_normal_matrix): the matrix
+    a model's normals go through under the model matrix ``m`` (column-major 16 floats)."""
+    M = np.ascontiguousarray(m, np.float32).reshape(16)
+    out = np.zeros(16, np.float32)
+    _check(N.host_lib().pnrt_normal_matrix(N.fptr(M), N.fptr(out)), "pnrt_normal_matrix")
+    return out
+
+
+def model_records(mesh: "Mesh") -> np.ndarray:
+    """A mesh's (nv, 8) MODEL-space records -- position 3, normal 3, texcoord 2 -- for
+    ``PathTracer.define_model``; zeros where the mesh has no normals or texcoords, as
+    pnrt_scene_add_mesh treats NULL."""
+    P = np.ascontiguousarray(mesh.positions, np.float32).reshape(-1, 3)
+    rec = np.zeros((len(P), 8), np.float32)
+    rec[:, 0:3] = P
+    if mesh.normals is not None:
+        rec[:, 3:6] = np.asarray(mesh.normals, np.float32).reshape(-1, 3)
+    if mesh.texcoords is not None:
+        rec[:, 6:8] = np.asarray(mesh.texcoords, np.float32).reshape(-1, 2)
+    return rec
+
+
 def camera_update(eye, center, up, fov: float, aspect: float) -> np.ndarray:
     """Camera::UpdateCamera (camera.hpp:11-31) -> (eye, llc, horizontal, vertical)."""
     f = lambda v: np.asarray(v, np.float32)  # noqa: E731

@@ -344,6 +344,22 @@ class InteractiveSession:
         self.pt.update_vertices(first, vertices, lights=lights, lights_sum_area=lights_sum_area)
         return self.frame(True)
 
+    def define_model(self, first: int, mesh) -> int:
+        """Tell the device which model vertices ``first`` .. hold: ``mesh``'s model-space records
+        (``host.model_records``) are kept there for ``move_model``.  Returns the model's id
+        (``PathTracer.define_model``)."""
+        from .host import model_records
+        return self.pt.define_model(first, model_records(mesh))
+
+    def move_model(self, model_id: int, ops, relight: bool = False):
+        """The gizmo drag: place the model under ``host.model_matrix(ops)`` on the device
+        (``PathTracer.place_models`` -- the matrix goes up, not the vertices), then the depth-1
+        redraw frame, as ``edit_vertices``.  ``relight`` when the model is a light whose area
+        changes.  Returns ``frame(True)``'s result."""
+        from .host import model_matrix
+        self.pt.place_models([(model_id, model_matrix(ops))], relight=relight)
+        return self.frame(True)
+
     def pick(self, px: int, py: int) -> dict:
         """What is under pixel (px, py) -- row 0 = bottom, as ``PathTracer.read_aov`` --: the
         decoded record (``tracer.decode_hits``, one ray: scalars and vectors) of the closest

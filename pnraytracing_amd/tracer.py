@@ -113,6 +113,45 @@ class PathTracer:
         self._ck(self._lib.pnrt_update_vertices_device(self._ctx, first, count, ctypes.c_void_p(ptr or 0), lp, ls),
                  "pnrt_update_vertices_device")
 
+    def define_model(self, first: int, model8) -> int:
+        """Keep a device copy of the (n, 8) MODEL-space records -- position 3, normal 3,
+        texcoord 2 (``host.model_records``) -- of vertices first .. first + n - 1, for
+        ``place_models`` (pnrt_define_model).  ``model8`` is a numpy array, or a torch
+        tensor on the context's device (pnrt_define_model_device).  Returns the model's id:
+        0, 1, 2, ... in definition order, until the next ``upload_scene``."""
+        mid = ctypes.c_int(-1)
+        if hasattr(model8, "data_ptr"):
+            if model8.dtype.itemsize != 4 or not model8.is_contiguous() or model8.numel() % 8:
+                raise ValueError("define_model: a contiguous float32 tensor of (n, 8) records")
+            self._ck(self._lib.pnrt_define_model_device(self._ctx, first, model8.numel() // 8, ctypes.c_void_p(model8.data_ptr()),
+                                                        ctypes.byref(mid)), "pnrt_define_model_device")
+        else:
+            rec = np.ascontiguousarray(model8, np.float32).reshape(-1, 8)
+            self._ck(self._lib.pnrt_define_model(self._ctx, first, len(rec), N.fptr(rec) if len(rec) else None, ctypes.byref(mid)),
+                     "pnrt_define_model")
+        return mid.value
+
+    def place_models(self, placements, relight: bool = False):
+        """Move models on the device: ``placements`` is a sequence of (id, matrix) with the
+        16 column-major floats ``host.model_matrix`` returns; every model's world-space
+        records are rewritten from its model-space copy and the BVH refit once
+        (pnrt_place_models; synchronous, as ``update_vertices``).  ``relight`` recomputes
+        the light list's prefix areas from the new positions -- every entry's; False keeps
+        them (no emissive triangle changed area).  Reset the accumulation afterwards."""
+        placements = list(placements)
+        arr = (N.Placement * max(len(placements), 1))()
+        for k, (mid, matrix) in enumerate(placements):
+            arr[k].model = int(mid)
+            arr[k].matrix[:] = np.asarray(matrix, np.float32).reshape(16).tolist()
+        self._ck(self._lib.pnrt_place_models(self._ctx, arr, len(placements), int(relight)), "pnrt_place_models")
+
+    def read_vertices(self, first: int, count: int) -> np.ndarray:
+        """The (count, 8) vertex records the device holds from ``first`` on: position 3,
+        normal 3, texcoord 2 -- floats 0-5 and 12-13 of a packed record (pnrt_read_vertices)."""
+        out = np.zeros((max(int(count), 0), 8), np.float32)
+        self._ck(self._lib.pnrt_read_vertices(self._ctx, first, count, N.fptr(out) if len(out) else None), "pnrt_read_vertices")
+        return out
+
     def read_bvh_boxes(self, nodes: np.ndarray) -> np.ndarray:
         """A copy of ``nodes`` -- the (nn, 12) pre-order node array that was uploaded -- with
         floats 0-5 of every node replaced by the box the device holds (pnrt_read_bvh_boxes)."""
