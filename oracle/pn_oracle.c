@@ -1,7 +1,7 @@
 /*
  * oracle/pn_oracle.c -- TEST INFRASTRUCTURE: CPU restatement of
  * shaders/ray_tracing.comp (PnRayTracing).  See pn_oracle.h for the pinning
- * status ("integrator parity unpinned by the reference itself").
+ * status (pinned to the shader text compiled as C++, oracle/shader/).
  *
  * Every function restates the GLSL it cites, in the GLSL's own evaluation
  * order (left-to-right binary ops, no contraction, IEEE binary32, correctly
@@ -601,10 +601,15 @@ static v3 SampleHDRImage(Ctx* c, v3* L, float* pdf) {
     return sample_rgb32f_clamp(s->hdr_rgb, s->hdr_w, s->hdr_h, xy);
 }
 
-/* TriangleSample (:598-624) */
-static Interaction TriangleSample(const Ctx* c, Triangle tri, f2 u) {
+/* UniformSampleTriangle (:598-601) */
+static f2 UniformSampleTriangle(f2 u) {
     float su0 = sqrtf(u.x);
     f2 b = {1.0f - su0, u.y * su0};
+    return b;
+}
+/* TriangleSample (:604-624) */
+static Interaction TriangleSample(const Ctx* c, Triangle tri, f2 u) {
+    f2 b = UniformSampleTriangle(u);
     v3 p0 = GetVertexPosition(c, tri.indices[0]);
     v3 p1 = GetVertexPosition(c, tri.indices[1]);
     v3 p2 = GetVertexPosition(c, tri.indices[2]);
@@ -924,6 +929,76 @@ int pno_render(const pno_scene* scene, const pno_frame* frame,
     free(per);
     if (stats) stats_add(stats, &total);
     return total.stack_overflow ? -6 : 0;
+}
+
+/* ---- pinning hook: the shading functions on caller inputs ------------------ */
+static const int SHADE_WORDS[22][2] = {
+    {33, 3}, {33, 5}, {15, 3}, {15, 3}, {10, 4}, {3, 6}, {2, 1}, {2, 1}, {5, 1}, {2, 1}, {5, 1}, {3, 2}, {3, 3},
+    {1, 8}, {1, 1}, {3, 10}, {2, 2}, {2, 2}, {4, 2}, {1, 2}, {2, 7}, {1, 18}};
+static inline float gf(const uint32_t** p) { float f; memcpy(&f, *p, 4); ++*p; return f; }
+static inline v3 g3(const uint32_t** p) { v3 r; r.x = gf(p); r.y = gf(p); r.z = gf(p); return r; }
+static inline void pf(uint32_t** o, float f) { memcpy(*o, &f, 4); ++*o; }
+static inline void p3(uint32_t** o, v3 v) { pf(o, v.x); pf(o, v.y); pf(o, v.z); }
+static Material gmat(const uint32_t** p) {
+    Material m;
+    m.emssive = g3(p); m.baseColor = g3(p);
+    m.subsurface = gf(p); m.metallic = gf(p); m.specular = gf(p);
+    m.specularTint = gf(p); m.roughness = gf(p); m.anisotropic = gf(p);
+    m.sheen = gf(p); m.sheenTint = gf(p); m.clearcoat = gf(p);
+    m.clearcoatGloss = gf(p); m.IOR = gf(p); m.transmission = gf(p);
+    return m;
+}
+
+int pno_shade_eval(const pno_scene* scene, const pno_frame* frame, int fn, const uint32_t* in, int n, uint32_t* out) {
+    if (!scene || !frame || !in || !out || n < 0 || fn < 0 || fn >= 22) return -1;
+    const int win = SHADE_WORDS[fn][0], wout = SHADE_WORDS[fn][1];
+    pno_stats st;
+    memset(&st, 0, sizeof st);
+    Ctx c;
+    memset(&c, 0, sizeof c);
+    c.s = scene; c.f = frame; c.st = &st;
+    for (int i = 0; i < n; ++i) {
+        const uint32_t* p = in + (size_t)win * i;
+        uint32_t* o = out + (size_t)wout * i;
+        switch (fn) {
+        case 0: { v3 V = g3(&p), N = g3(&p), L = g3(&p), X = g3(&p), Y = g3(&p); Material m = gmat(&p);
+                  p3(&o, DisneyBRDF(V, N, L, X, Y, &m)); break; }
+        case 1: { c.seed = *p++; v3 V = g3(&p), N = g3(&p), T = g3(&p), B = g3(&p); Material m = gmat(&p);
+                  float r1 = gf(&p), r2 = gf(&p), pdf = 0.0f;
+                  v3 L = SampleDisneyBRDF(&c, V, N, T, B, &m, r1, r2, &pdf); p3(&o, L); pf(&o, pdf); *o++ = c.seed; break; }
+        case 2: case 3: { v3 nn = g3(&p), t = g3(&p), b = g3(&p), v = g3(&p); float r1 = gf(&p), r2 = gf(&p), a = gf(&p);
+                  p3(&o, fn == 2 ? SampleGTR1(nn, t, b, v, r1, r2, a) : SampleGTR2(nn, t, b, v, r1, r2, a)); break; }
+        case 4: { c.seed = *p++; v3 nn = g3(&p), t = g3(&p), b = g3(&p);
+                  p3(&o, SampleCosineHemisphere(&c, nn, t, b)); *o++ = c.seed; break; }
+        case 5: { v3 nn = g3(&p), t, b; BuildTangentSpace(nn, &t, &b); p3(&o, t); p3(&o, b); break; }
+        case 6: { float a = gf(&p), b = gf(&p); pf(&o, GTR1(a, b)); break; }
+        case 7: { float a = gf(&p), b = gf(&p); pf(&o, GTR2(a, b)); break; }
+        case 8: { float a = gf(&p), b = gf(&p), d = gf(&p), e = gf(&p), f = gf(&p); pf(&o, GTR2_aniso(a, b, d, e, f)); break; }
+        case 9: { float a = gf(&p), b = gf(&p); pf(&o, smithG_GGX(a, b)); break; }
+        case 10: { float a = gf(&p), b = gf(&p), d = gf(&p), e = gf(&p), f = gf(&p); pf(&o, smithG_GGX_aniso(a, b, d, e, f)); break; }
+        case 11: { f2 uv = toSphericalCoord(g3(&p)); pf(&o, uv.x); pf(&o, uv.y); break; }
+        case 12: p3(&o, GetHDRImageColor(&c, g3(&p))); break;
+        case 13: { c.seed = *p++; v3 L = V3(0.0f, 0.0f, 0.0f), col = L; float pdf = 0.0f;
+                   if (scene->has_hdr) col = SampleHDRImage(&c, &L, &pdf);
+                   p3(&o, col); p3(&o, L); pf(&o, pdf); *o++ = c.seed; break; }
+        case 14: *o++ = (uint32_t)GetLightIndex(&c, gf(&p)); break;
+        case 15: { int t = (int)*p++; f2 u; u.x = gf(&p); u.y = gf(&p);
+                   Interaction r = TriangleSample(&c, GetTriangle(&c, t), u);
+                   p3(&o, r.position); p3(&o, r.normal); pf(&o, r.texcoord.x); pf(&o, r.texcoord.y);
+                   *o++ = (uint32_t)r.textureId; *o++ = (uint32_t)r.materialId; break; }
+        case 16: { f2 u; u.x = gf(&p); u.y = gf(&p); f2 b = UniformSampleTriangle(u); pf(&o, b.x); pf(&o, b.y); break; }
+        case 17: { uint32_t k = *p++, b = *p++; f2 r = sobolVec2(k, b); pf(&o, r.x); pf(&o, r.y); break; }
+        case 18: { c.px = (int)*p++; c.py = (int)*p++; f2 q; q.x = gf(&p); q.y = gf(&p);
+                   q = CranleyPattersonRotation(&c, q); pf(&o, q.x); pf(&o, q.y); break; }
+        case 19: { uint32_t sd = *p++; uint32_t r = pno_wang_hash(&sd); *o++ = r; *o++ = sd; break; }
+        case 20: { float s = gf(&p), t = gf(&p); Ray r = CameraGetRay(&c, s, t); p3(&o, r.origin); p3(&o, r.dir); pf(&o, r.tMax); break; }
+        default: { Material m = GetMaterial(&c, (int)*p++); p3(&o, m.emssive); p3(&o, m.baseColor);
+                   pf(&o, m.subsurface); pf(&o, m.metallic); pf(&o, m.specular); pf(&o, m.specularTint); pf(&o, m.roughness);
+                   pf(&o, m.anisotropic); pf(&o, m.sheen); pf(&o, m.sheenTint); pf(&o, m.clearcoat); pf(&o, m.clearcoatGloss);
+                   pf(&o, m.IOR); pf(&o, m.transmission); break; }
+        }
+    }
+    return wout;
 }
 
 /* ---- math parity helper --------------------------------------------------- */

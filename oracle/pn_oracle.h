@@ -13,12 +13,15 @@
  *     scene over C1/C2/C4/C5, with the three documented rule differences
  *     (ties, slab clipping, glm::normalize) switched by pno_intersect's `sem`
  *     (tests/test_isect_pin.py).
- *   - The shading half (Disney BRDF, sampling, MIS, env lookups): unpinned by
- *     the reference itself (the GLSL cannot execute in this container -- no
- *     GL 4.5 context / no glslang -- and the reference has no CPU version of
- *     it and no golden images or tests).  Its faithfulness rests on
- *     line-by-line restatement of ray_tracing.comp, with every function
- *     citing the lines it follows.
+ *   - The shading half (Disney BRDF and its sampling, light and environment
+ *     sampling, MIS, the path loop, the order of the RNG draws) and the
+ *     intersection code under the GLSL's own rules (sem 0): PINNED bit for bit
+ *     to the shader's own text.  shaders/ray_tracing.comp is translated to C++
+ *     by text surgery and compiled here (oracle/shader/, oracle/_ref/
+ *     shader_driver); pno_shade_eval, pno_intersect and pno_render equal it
+ *     word for word per function and per image (tests/test_shader_pin.py).
+ *     What stays by definition is what the text does not carry: the built-ins
+ *     (libm, vector forms, min/max, samplers), listed in DESIGN.md 7.
  *
  * Inputs are the reference's own flattened float arrays exactly as main.cpp
  * packs them (main.cpp:409-524): vertex 15 f, material 18 f, triangle 6 f,
@@ -101,6 +104,34 @@ void pno_math_eval(int fn, const float* a, const float* b, float* out, int n);
  * kind 4 with sem & 2: hit, t0, t1.  Returns 0, -1 bad args, -6 stack overflow. */
 int pno_intersect(const pno_scene* scene, const float* rays, int n, int kind, int sem,
                   const int* idx, uint32_t* out, int threads);
+
+/* Pinning hook (tests only): one of the shading functions pno_render itself
+ * runs, on n caller records of 32-bit words (floats as bits); tests/test_shader_pin.py
+ * compares the words with those of the reference's shader text compiled as C++
+ * (oracle/shader/shader_driver.cpp `FUNC`, the same table).  Material = the 18
+ * floats of the struct in declaration order (:19-26), set directly.
+ *  fn  function (ray_tracing.comp)   words in                          words out
+ *   0  DisneyBRDF                    V N L X Y Material (33)           3
+ *   1  SampleDisneyBRDF              seed V N T B Material r1 r2 (33)  L pdf seed (5)
+ *   2  SampleGTR1   3 SampleGTR2     n t b v r1 r2 alpha (15)          3
+ *   4  SampleCosineHemisphere        seed n t b (10)                   dir seed (4)
+ *   5  BuildTangentSpace             n (3)                             t b (6)
+ *   6  GTR1   7 GTR2   9 smithG_GGX  2                                 1
+ *   8  GTR2_aniso  10 smithG_GGX_aniso  5                              1
+ *  11  toSphericalCoord              v (3)                             2
+ *  12  GetHDRImageColor              v (3)                             3
+ *  13  SampleHDRImage                seed (1)                          colour L pdf seed (8)
+ *  14  GetLightIndex                 u (1)                             index (1)
+ *  15  TriangleSample                triangle u (3)                    position normal texcoord textureId materialId (10)
+ *  16  UniformSampleTriangle         u (2)                             2
+ *  17  sobolVec2                     i b (2)                           2
+ *  18  CranleyPattersonRotation      x y p (4)                         2
+ *  19  wang_hash                     seed (1)                          value seed (2)
+ *  20  CameraGetRay                  s t (2)                           origin dir tMax (7)
+ *  21  GetMaterial                   index (1)                         Material (18)
+ * Returns the words written per record, or -1 on bad arguments. */
+int pno_shade_eval(const pno_scene* scene, const pno_frame* frame, int fn,
+                   const uint32_t* in, int n, uint32_t* out);
 
 /* Known-answer helpers. */
 uint32_t pno_wang_hash(uint32_t* seed);

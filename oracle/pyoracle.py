@@ -96,6 +96,9 @@ def lib():
         L.pno_intersect.restype = ctypes.c_int
         L.pno_intersect.argtypes = [ctypes.POINTER(Scene), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.pno_shade_eval.restype = ctypes.c_int
+        L.pno_shade_eval.argtypes = [ctypes.POINTER(Scene), ctypes.POINTER(Frame), ctypes.c_int, ctypes.c_void_p,
+                                     ctypes.c_int, ctypes.c_void_p]
         L.pno_sobol.restype = ctypes.c_float
         L.pno_sobol.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
         _lib = L
@@ -167,6 +170,18 @@ class Oracle:
             raise RuntimeError(f"pno_render failed ({rc})")
         return accum, st.as_dict()
 
+    def shade_eval(self, fn: int, words: np.ndarray) -> np.ndarray:
+        """One shading function of the oracle on n records of 32-bit words
+        (pn_oracle.h pno_shade_eval); returns (n, words out) u32."""
+        win, wout = SHADE_WORDS[fn]
+        words = np.ascontiguousarray(words, np.uint32).reshape(-1, win)
+        out = np.zeros((len(words), wout), np.uint32)
+        rc = lib().pno_shade_eval(ctypes.byref(self.scene), ctypes.byref(self.frame), fn, words.ctypes.data,
+                                  len(words), out.ctypes.data)
+        if rc != wout:
+            raise RuntimeError(f"pno_shade_eval failed ({rc})")
+        return out
+
     def intersect(self, rays: np.ndarray, kind: int, sem: int, idx: np.ndarray | None = None,
                   threads: int = 0) -> np.ndarray:
         """The oracle's intersection routines on caller rays (pn_oracle.h
@@ -186,6 +201,11 @@ class Oracle:
         if rc != 0:
             raise RuntimeError(f"pno_intersect failed ({rc})")
         return out
+
+
+# pno_shade_eval's table (pn_oracle.h): fn -> (words in, words out)
+SHADE_WORDS = [(33, 3), (33, 5), (15, 3), (15, 3), (10, 4), (3, 6), (2, 1), (2, 1), (5, 1), (2, 1), (5, 1), (3, 2), (3, 3),
+               (1, 8), (1, 1), (3, 10), (2, 2), (2, 2), (4, 2), (1, 2), (2, 7), (1, 18)]
 
 
 def math_eval(fn: int, a: np.ndarray, b: np.ndarray | None = None) -> np.ndarray:

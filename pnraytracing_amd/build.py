@@ -4,6 +4,7 @@
     libpnrt.so       hipcc csrc/pnrt_device.hip, gfx950     (device library)
     oracle/liboracle.so    gcc (TEST-ONLY parity oracle; see oracle/)
     oracle/_ref/ref_driver g++ on /root/reference headers (only where present)
+    oracle/_ref/shader_driver g++ on the reference's compute shader, translated (only where present)
 
 Floating point: every library is built with -ffp-contract=off and without
 fast-math so the HIP kernel, the host library and the oracle evaluate the
@@ -206,6 +207,9 @@ def build_oracle(force=False):
     ref = os.environ.get("PNRT_REFERENCE", "/root/reference")
     if os.path.isdir(os.path.join(ref, "include")):
         _run(["make", "-s", "-C", os.path.join(odir, "ref"), f"REF={ref}"] + (["-B"] if force else []))
+    # the reference's compute shader, translated to C++ where it lies: oracle/_ref/shader_driver
+    if os.path.isfile(os.path.join(ref, "shaders", "ray_tracing.comp")):
+        _run(["make", "-s", "-C", os.path.join(odir, "shader"), f"REF={ref}", f"PYTHON={sys.executable}"] + (["-B"] if force else []))
 
 
 def build_all(force=False):
