@@ -10,7 +10,8 @@ Sources of truth, all from the reference itself:
   * SURVEY.md 8c -- probe values recorded from the reference's LoadHDRImage
     (sha256 prefixes/suffixes and spot entries of the RGB and RandomHDR blobs).
 
-Usage:  python tests/golden/make_golden.py
+Usage:  python tests/golden/make_golden.py          (every fixture)
+        python tests/golden/make_golden.py lamps    (lamps_reference_arrays.npz alone)
 """
 from __future__ import annotations
 
@@ -63,8 +64,9 @@ def driver_input(rec: Recorder, cam_args) -> bytes:
         nv = len(m.positions)
         out.append(struct.pack("<i", nv))
         out.append(np.ascontiguousarray(m.positions, "<f4").tobytes())
-        out.append(np.ascontiguousarray(m.normals, "<f4").tobytes())
-        out.append(np.ascontiguousarray(m.texcoords, "<f4").tobytes())
+        # (a mesh without normals or texcoords: zeros, as pnrt_scene_add_mesh takes NULL)
+        out.append(np.ascontiguousarray(np.zeros((nv, 3)) if m.normals is None else m.normals, "<f4").tobytes())
+        out.append(np.ascontiguousarray(np.zeros((nv, 2)) if m.texcoords is None else m.texcoords, "<f4").tobytes())
         out.append(struct.pack("<i", len(m.indices)))
         out.append(np.ascontiguousarray(m.indices, "<i4").tobytes())
     eye, center, up, fov, aspect = cam_args
@@ -127,9 +129,28 @@ SCENES = [("C2", S.bunny_c2, CORNELL_CAM + (ASPECT_1080,), {"env": False}),
           ("C5", S.synthetic_c5, CORNELL_CAM + (ASPECT_2160,), {"env": False})]
 
 
-def main():
+def build_driver():
     if not os.path.exists(DRIVER):
         subprocess.run(["make", "-C", os.path.join(REPO, "oracle", "ref"), f"REF={REF}"], check=True)
+
+
+def lamps():
+    """tests/lamps_common.py two_lamps_scene(150, 148): full arrays from the reference build -- a light
+    list of 300 entries, the float prefix of main.cpp:374-383 over all of them.  Writes
+    lamps_reference_arrays.npz and nothing else."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import lamps_common as L
+    build_driver()
+    rec = Recorder()
+    L.add_two_lamps(rec, 150, 148)
+    rec.build()
+    ref = run_driver(driver_input(rec, CORNELL_CAM + (float(np.float32(32) / np.float32(24)),)))
+    np.savez_compressed(os.path.join(HERE, "lamps_reference_arrays.npz"), **ref, materials=np.stack(rec.mats))
+    print("lamps:", {k: v.shape for k, v in ref.items()})
+
+
+def main():
+    build_driver()
     fixtures = {}
 
     # ---- C1: full arrays from the reference build -----------------------------------------
@@ -183,7 +204,11 @@ def main():
     }
     json.dump(fixtures, open(os.path.join(HERE, "reference_fixtures.json"), "w"), indent=1)
     print("wrote", os.path.join(HERE, "reference_fixtures.json"))
+    lamps()
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["lamps"]:
+        lamps()
+    else:
+        main()

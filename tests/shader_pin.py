@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.join(REPO, "oracle"))
 sys.path.insert(0, HERE)
 
 import isect_rays as IR  # noqa: E402
+import lamps_common as LAMPS  # noqa: E402
 import pyoracle  # noqa: E402
 from pnraytracing_amd import host as H  # noqa: E402
 from pnraytracing_amd import scenes as S  # noqa: E402
@@ -155,6 +156,7 @@ def image_cases():
     cases["coincident130"] = (lambda: (coincident_scene(130), 0, 3), True)
     cases["emission1e-30"] = (lambda: extreme_scene(206, -30), False)
     cases["emission1e25"] = (lambda: extreme_scene(205, 25), False)
+    cases["lamp65/f0x3"] = (lambda: (LAMPS.lamp_scene(63), 0, 3), True)           # 65 lights: GetLightIndex's search, not a scan
     return cases
 
 
@@ -365,6 +367,13 @@ def fn_cases(cfgs):
         cases[f"TriangleIntersectP/{key}"] = (24, key, fw(rays, idx))
         rays, idx = IR.make_pairs(cfg.packed, 6000, SEED, "box")
         cases[f"BoundIntersect/{key}"] = (22, key, fw(rays, idx))
+
+    # a list of 300: the u of the short lists, then every prefix area over the sum and its float neighbours
+    # (ties and boundaries of the search); no draw from rng, which the cases above share
+    p = cfgs["lamp300"].packed
+    edge = (p.lights[:, 1].astype(F) / F(p.lights_sum_area)).astype(F)
+    ul = np.concatenate([u, edge, np.nextafter(edge, F(0)), np.nextafter(edge, F(2))]).astype(F)
+    cases["GetLightIndex/lamp300"] = (14, "lamp300", fw(ul))
     return cases
 
 
@@ -382,7 +391,7 @@ def fn_scenes():
         return dataclasses.replace(c1, packed=dataclasses.replace(c1.packed, lights=L, lights_sum_area=total))
     i0, i1 = float(idx[0]), float(idx[-1])
     return {"fuzz": fuzz, "C1": c1, "C3": S.marry_c3(96, 54), "C4": S.teapot_c4(96, 54), "coincident": coincident_scene(130),
-            "lights0": with_lights([]), "lights1": with_lights([(i0, 2.5, 0)]),
+            "lamp300": LAMPS.lamp_scene(298), "lights0": with_lights([]), "lights1": with_lights([(i0, 2.5, 0)]),
             # equal prefix areas: entries 1 and 3 repeat their predecessor's (zero-area lights)
             "lights5": with_lights([(i0, 1, 0), (i1, 1, 0), (3, 2, 0), (4, 2, 0), (5, 3, 0)])}
 

@@ -2,10 +2,12 @@
 
 Every Disney parameter drawn at random per material (metallic, clearcoat,
 anisotropic, sheen, subsurface, roughness down to 0 ...), triangle soups and
-quads with and without vertex normals, several emissive materials (multi-
-light binary search) or none at all (GetLightIndex -> -1), environment on and
-off, RGB/RGBA/grey textures of odd widths on some meshes, odd image sizes and
-row-band shards, depth 1..4 -- the cases the fixed C1-C5 scenes do not reach.
+quads with and without vertex normals, several emissive materials (up to
+eight light triangles: the scan of pt_wf.h light_entry, never its binary
+search -- tests/test_gpu_lights.py has the longer lists) or none at all
+(GetLightIndex -> -1), environment on and off, RGB/RGBA/grey textures of odd
+widths on some meshes, odd image sizes and row-band shards, depth 1..4 -- the
+cases the fixed C1-C5 scenes do not reach.
 """
 import os
 

@@ -37,7 +37,7 @@ def golden():
 
 
 def test_cases_are_the_ones_asked_for():
-    want = {"C1/d4/f0x4", "C1/d4/f255x2", "C3/f0x2", "C4/f0x2", "coincident130"} | {f"fuzz{s}" for s in SP.GPU_FUZZ_SEEDS}
+    want = {"C1/d4/f0x4", "C1/d4/f255x2", "C3/f0x2", "C4/f0x2", "coincident130", "lamp65/f0x3"} | {f"fuzz{s}" for s in SP.GPU_FUZZ_SEEDS}
     assert set(CASES) == want and len(SP.GPU_FUZZ_SEEDS) == 4
 
 

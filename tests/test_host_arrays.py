@@ -34,6 +34,26 @@ def test_c1_arrays_bitwise_equal_reference_build():
     np.testing.assert_array_equal(bits(p.materials), bits(ref["materials"]))
 
 
+def test_lamps_arrays_bitwise_equal_reference_build():
+    """tests/lamps_common.py two_lamps_scene(150, 148): a light list of 300 entries, so the float prefix
+    (area + previous prefix, main.cpp:374-383) runs over all of them -- in build_lights, and again in
+    pnrt_scene_relight for the unmoved lamp."""
+    import lamps_common as L
+    ref = np.load(os.path.join(GOLD, "lamps_reference_arrays.npz"))
+    p = L.two_lamps_scene(150, 148).packed
+    assert len(ref["lights"]) == 300 and np.count_nonzero(np.diff(ref["lights"][:, 1]) > 0) > 250
+    for k in ("vertices", "triangles", "nodes", "lights"):
+        np.testing.assert_array_equal(bits(getattr(p, k)), bits(ref[k]), err_msg=k)
+    np.testing.assert_array_equal(bits(p.materials), bits(ref["materials"]))
+    assert bits(np.float32(p.lights_sum_area)) == bits(ref["lights"][-1, 1])             # main.cpp:392
+    mesh = L.soup(150, 11, (0, 3, 0))
+    again = H.refit_packed(p, L.LAMP_FIRST_VERTEX, H.model_vertices(mesh, L.LAMP_A_OPS))
+    np.testing.assert_array_equal(bits(again.vertices), bits(ref["vertices"]))
+    np.testing.assert_array_equal(bits(again.triangles), bits(ref["triangles"]))
+    np.testing.assert_array_equal(bits(again.lights), bits(ref["lights"]), err_msg="pnrt_scene_relight")
+    assert bits(np.float32(again.lights_sum_area)) == bits(ref["lights"][-1, 1])
+
+
 def test_c1_bvh_shape_matches_survey_probe():
     # SURVEY.md 8(a) a22: 9 nodes, BVH-order materials 3 3 0 0 1 1 2 2 4 4 5 5, root axis 1 right 8
     p = S.cornell_c1().packed
