@@ -580,13 +580,64 @@ static int report_trace_diag(pnrt_ctx* c, const WfBufs& b, hipStream_t st, int b
     return PNRT_OK;
 }
 
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a kernel's template argument
+template <class F>
+static void with_bool(bool v, F&& f) {
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+#define CAM_REC_BYTES 48       // pt_primary_wf's record (q0, q1, q2), one per path slot of a camera batch
+// Where a call's first-bounce rays come from, made once by its entry point and passed down unchanged:
+// the pipe's per-pixel primary records (PrimKey), a camera per frame (pt_cameras.h) or the caller's ray
+// sets (pt_rays.h); and, independently, whether its path slots are an active-tile list (pt_adaptive.h).
+// Only the calls the ABI has can be made: cameras take no tile list.
+class PathSource {
+    PathSource(int k, const WfAdapt* t, const float* cm, const void* ry, int64_t stride)
+        : kind(k), tiles(t), cams(cm), rays(static_cast<const float4*>(ry)), ray_stride(stride) {}
+
+public:
+    enum { RECORDS, CAMERAS, RAYS };
+    const int kind;
+    const WfAdapt* const tiles;    // an adaptive call's active-tile list, or null
+    const float* const cams;       // CAMERAS: the call's cameras (pinned host memory, 12 floats per frame)
+    const float4* const rays;      // RAYS: the call's first set (device memory),
+    const int64_t ray_stride;      // and the records between the sets of consecutive frames
+    static PathSource records(const WfAdapt* tiles = nullptr) { return {RECORDS, tiles, nullptr, nullptr, 0}; }
+    static PathSource cameras(const float* cams) { return {CAMERAS, nullptr, cams, nullptr, 0}; }
+    static PathSource ray_sets(const void* rays, int64_t stride, const WfAdapt* tiles = nullptr) {
+        return {RAYS, tiles, nullptr, rays, stride};
+    }
+    // further bytes per path slot: the batch's camera-ray records, one per slot
+    size_t slot_bytes() const { return kind == RECORDS ? 0 : CAM_REC_BYTES; }
+    // the call reads the pipe's per-pixel records, traced or still valid by their key
+    bool per_pixel_records() const { return kind == RECORDS; }
+    // the call's workers read what the caller queued on the context stream before it (ev_rays)
+    bool after_caller_stream() const { return kind == RAYS; }
+    // f(the tile list), or f(): the pack pt_rays_wf ends with
+    template <class F>
+    void with_tiles(F&& f) const {
+        if (tiles) f(*tiles);
+        else f();
+    }
+    // f(the pack the gen and shade kernels end with) for a batch with the camera table cm or the rays ry:
+    // one of (), (WfAdapt), (WfCams), (WfRays), (WfAdapt, WfRays)
+    template <class F>
+    void with_pack(const WfCams& cm, const WfRays& ry, F&& f) const {
+        switch (kind) {
+            case RECORDS: with_tiles(f); break;
+            case CAMERAS: f(cm); break;
+            case RAYS: with_tiles([&](auto... t) { f(t..., ry); }); break;
+        }
+    }
+};
+
 // One batch of frames (gen -> {trace -> shade/setup} x depth) on one stream;
-// its colours land in frame slots [0, cf) of `colors`.
+// its colours land in frame slots [0, cf) of `colors`.  cm, ry: the batch's camera table or rays, as
+// src takes them (then primary = the batch's records per slot).
 static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const WfLayout& L, hipStream_t st,
-                        const float4* primary, float4* colors, bool alone, bool one, hipEvent_t stage = nullptr,
-                        const WfAdapt* ad = nullptr,       // ad: an adaptive batch's slots (pt_adaptive.h); with ry: over its rays
-                        const WfCams* cm = nullptr,        // cm: a camera batch's table (pt_cameras.h; primary = its records)
-                        const WfRays* ry = nullptr) {      // ry: a ray batch's rays (pt_rays.h; primary = its records)
+                        const float4* primary, float4* colors, bool alone, bool one, hipEvent_t stage, const PathSource& src,
+                        const WfCams& cm, const WfRays& ry) {
     WfBufs b = L.b;
     if (b.n > WF_META_SLOT) return set_err(c, PNRT_E_ARG, "render: too many paths per batch");
     // the cooperative finish of closest-hit rays pays where the drain leaves the chip
@@ -595,20 +646,18 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
     // save (C2 -2.3 %), so pipelined calls run the instantiation without it
     // (only for batches below WF_CC_MAX_PATHS: the lone call's instantiation runs at
     // WF_TRACE_WAVES_CC waves per SIMD, fewer than a large batch's stepping wants)
-    const bool cc = alone && WF_COOP_TAIL >= 2 && (size_t)b.n < (size_t)WF_CC_MAX_PATHS;
+    const bool cc = alone && WF_COOP_TAIL >= 2 && (size_t)b.n < (size_t)WF_CC_MAX_PATHS && !s.has_leaf_table;
     const dim3 g((unsigned)((b.n + 255) / 256));
     b.wr = L.set[0];
     if (WF_STATS) HIPCHK(c, hipMemsetAsync(b.stats + 56, 0, 64, st));    // the setups' moot-ray counts
     {   // path state + bounce-0 sampling
         ProfScope ps(c, PNRT_K_GEN, st);
-        if (ad && ry) hipLaunchKernelGGL((pt_wf_gen_setup<WfAdapt, WfRays>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad, *ry);
-        else if (ad) hipLaunchKernelGGL(pt_wf_gen_setup<WfAdapt>, g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
-        else if (cm) hipLaunchKernelGGL(pt_wf_gen_setup<WfCams>, g, dim3(256), 0, st, s, fp, b, primary, colors, *cm);
-        else if (ry) hipLaunchKernelGGL(pt_wf_gen_setup<WfRays>, g, dim3(256), 0, st, s, fp, b, primary, colors, *ry);
-        else hipLaunchKernelGGL(pt_wf_gen_setup<>, g, dim3(256), 0, st, s, fp, b, primary, colors);
+        src.with_pack(cm, ry, [&](auto... pk) {
+            hipLaunchKernelGGL((pt_wf_gen_setup<decltype(pk)...>), g, dim3(256), 0, st, s, fp, b, primary, colors, pk...);
+        });
     }
     HIPCHK(c, hipGetLastError());
-    const unsigned tg = trace_grid_for(c, b.n, alone, one, cc && !s.has_leaf_table);
+    const unsigned tg = trace_grid_for(c, b.n, alone, one, cc);
     // (launch position 2 b: bounce b's trace, 2 b + 1: its shade)
     const int stage_at = std::max(2 * fp.max_depth - WF_STAGGER, 0);
     for (int bounce = 0; bounce < fp.max_depth; ++bounce) {
@@ -619,11 +668,13 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
             HIPCHK(c, hipMemsetAsync(b.counter, 0, WF_COUNTER_BYTES + (WF_STATS ? 448 : 512), st));
         {
             ProfScope ps(c, PNRT_K_TRACE, st);
-            if (s.has_leaf_table)       // (the kernel is instantiated per scene kind)
-                hipLaunchKernelGGL((pt_wf_trace<WF_STACK, true>), dim3(tg), dim3(WF_TRACE_BLOCK), 0, st, s, b, fp.mode);
-            else if (cc)
+            if (cc)                     // (only scenes without a leaf table have the instantiation)
                 hipLaunchKernelGGL((pt_wf_trace<WF_STACK, false, true>), dim3(tg), dim3(WF_TRACE_BLOCK), 0, st, s, b, fp.mode);
-            else hipLaunchKernelGGL((pt_wf_trace<WF_STACK, false>), dim3(tg), dim3(WF_TRACE_BLOCK), 0, st, s, b, fp.mode);
+            else
+                with_bool(s.has_leaf_table, [&](auto tbl) {
+                    hipLaunchKernelGGL((pt_wf_trace<WF_STACK, decltype(tbl)::value>), dim3(tg), dim3(WF_TRACE_BLOCK), 0, st, s, b,
+                                       fp.mode);
+                });
         }
         HIPCHK(c, hipGetLastError());
         if (WF_STATS || WF_TIMING || WF_DIAG_COOP || WF_DIAG_COOPSTAT)
@@ -634,32 +685,18 @@ static int render_batch(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, c
             // MIS + continuation, then the next bounce's sampling (sets alternate)
             b.rd = L.set[bounce & 1];
             b.wr = L.set[(bounce + 1) & 1];
-            const bool fin = bounce + 1 == fp.max_depth;   // every path ends: no setup half, no rays
             // this setup's moot test drops light rays, and continuation rays where it sets up
             // the last bounce: those kinds go through their entry lists, in the setup and in
             // the trace launch that follows it (gen has no test: whole ranges, no lists)
             b.lidx = L.lidx;
             b.cidx = bounce + 2 == fp.max_depth ? L.cidx : nullptr;
-            if (ad && ry && fin)
-                hipLaunchKernelGGL((pt_wf_shade_setup<true, WfAdapt, WfRays>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad, *ry);
-            else if (ad && ry)
-                hipLaunchKernelGGL((pt_wf_shade_setup<false, WfAdapt, WfRays>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad, *ry);
-            else if (ad && fin)
-                hipLaunchKernelGGL((pt_wf_shade_setup<true, WfAdapt>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
-            else if (ad)
-                hipLaunchKernelGGL((pt_wf_shade_setup<false, WfAdapt>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ad);
-            else if (cm && fin)
-                hipLaunchKernelGGL((pt_wf_shade_setup<true, WfCams>), g, dim3(256), 0, st, s, fp, b, primary, colors, *cm);
-            else if (cm)
-                hipLaunchKernelGGL((pt_wf_shade_setup<false, WfCams>), g, dim3(256), 0, st, s, fp, b, primary, colors, *cm);
-            else if (ry && fin)
-                hipLaunchKernelGGL((pt_wf_shade_setup<true, WfRays>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ry);
-            else if (ry)
-                hipLaunchKernelGGL((pt_wf_shade_setup<false, WfRays>), g, dim3(256), 0, st, s, fp, b, primary, colors, *ry);
-            else if (fin)
-                hipLaunchKernelGGL(pt_wf_shade_setup<true>, g, dim3(256), 0, st, s, fp, b, primary, colors);
-            else
-                hipLaunchKernelGGL(pt_wf_shade_setup<false>, g, dim3(256), 0, st, s, fp, b, primary, colors);
+            // (the last bounce's: every path ends -- no setup half, no rays)
+            with_bool(bounce + 1 == fp.max_depth, [&](auto fin) {
+                src.with_pack(cm, ry, [&](auto... pk) {
+                    hipLaunchKernelGGL((pt_wf_shade_setup<decltype(fin)::value, decltype(pk)...>), g, dim3(256), 0, st, s, fp, b,
+                                       primary, colors, pk...);
+                });
+            });
         }
         HIPCHK(c, hipGetLastError());
     }
@@ -687,9 +724,8 @@ static bool parse_batch_bytes(const char* s, uint64_t* out) {
 static size_t frame_paths(int width, int rows) {
     return (size_t)((width + 7) / 8) * (size_t)((rows + 7) / 8) * 64;
 }
-// (per_path: further bytes per path slot -- pnrt_render_cameras' camera-ray records)
-#define CAM_REC_BYTES 48       // pt_primary_wf's record (q0, q1, q2), one per path slot of a camera batch
-static size_t batch_bytes(size_t per_frame, size_t pix, uint32_t k, size_t per_path = 0) {
+// (per_path: further bytes per path slot -- PathSource::slot_bytes)
+static size_t batch_bytes(size_t per_frame, size_t pix, uint32_t k, size_t per_path) {
     return wf_bytes(per_frame * k) + pix * 16 * k + per_frame * k * per_path;
 }
 // Frames per batch of a call of nf frames (the one plan: render_wavefront and
@@ -697,7 +733,7 @@ static size_t batch_bytes(size_t per_frame, size_t pix, uint32_t k, size_t per_p
 // fits the path state's slot field (large frames take fewer per batch), and under
 // PNRT_BATCH_BYTES the largest count whose batch_bytes fit the cap -- one frame when
 // not even one does.  0: a frame too large for one batch.
-static uint32_t plan_chunk(const pnrt_ctx* c, size_t per_frame, size_t pix, uint32_t nf, size_t per_path = 0) {
+static uint32_t plan_chunk(const pnrt_ctx* c, size_t per_frame, size_t pix, uint32_t nf, size_t per_path) {
     if (per_frame == 0 || per_frame > (size_t)WF_META_SLOT) return 0;
     const uint32_t fit = (uint32_t)std::min<size_t>(WF_MAX_CHUNK_FRAMES, (size_t)WF_META_SLOT / per_frame);
     uint32_t chunk = nf < fit ? nf : fit;
@@ -809,38 +845,50 @@ static bool prim_key_eq(const pnrt_ctx::PrimKey& have, const pnrt_ctx::PrimKey& 
            (any_band || have.band == want.band) && have.n_shards == want.n_shards && have.shard == want.shard &&
            have.mode == want.mode;
 }
+// `b` with the trace kernel's spill area `ovf` (sized by ovf_size, after trace_grid_init) and the fault words
+static WfBufs spill_bufs(const pnrt_ctx* c, uint2* ovf, WfBufs b = WfBufs{}) {
+    b.ovf = ovf;
+    b.fault = c->fault_dev;
+    b.ovf_stride = (uint32_t)ovf_size(c).stride;
+    return b;
+}
+// One launch of the trace kernel's step over n items, grid-stride, on stream st: launch(TBL, grid) names
+// the kernel.  Class PNRT_K_PRIMARY.
+template <class L>
+static int trace_step(pnrt_ctx* c, const DevScene& s, hipStream_t st, size_t n, L&& launch) {
+    ProfScope ps(c, PNRT_K_PRIMARY, st);
+    const dim3 grid((unsigned)std::min<size_t>((n + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid));
+    with_bool(s.has_leaf_table, [&](auto tbl) { launch(tbl, grid); });
+    HIPCHK(c, hipGetLastError());
+    return PNRT_OK;
+}
+
 // Ensure `primary` holds the records of fp's shard (render_wavefront's pipes and
 // pnrt_render_guides): traced on stream w -- the trace kernel's step, grid-stride,
 // with the spill area `ovf` -- unless `have` says they are there already.  One
 // launch of class PNRT_K_PRIMARY, or none.
-static int ensure_primary(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, hipStream_t w, uint2* ovf, int ovf_stride,
-                          float4* primary, pnrt_ctx::PrimKey& have) {
+static int ensure_primary(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, hipStream_t w, uint2* ovf, float4* primary,
+                          pnrt_ctx::PrimKey& have) {
     const pnrt_ctx::PrimKey key = prim_key(c, fp);
-    if (!prim_key_eq(have, key)) {
-        ProfScope ps(c, PNRT_K_PRIMARY, w);
-        const size_t pix = (size_t)fp.rows * fp.width;
-        WfBufs pb{};
-        pb.ovf = ovf;
-        pb.fault = c->fault_dev;
-        pb.ovf_stride = (uint32_t)ovf_stride;
-        const unsigned gp = (unsigned)std::min<size_t>((pix + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
-        if (s.has_leaf_table)
-            hipLaunchKernelGGL((pt_primary_wf<WF_STACK, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, pb, primary);
-        else hipLaunchKernelGGL((pt_primary_wf<WF_STACK, false>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, pb, primary);
-        HIPCHK(c, hipGetLastError());
-        have = key;
-    }
+    if (prim_key_eq(have, key)) return PNRT_OK;
+    const WfBufs pb = spill_bufs(c, ovf);
+    const auto launch = [&](auto tbl, dim3 grid) {
+        hipLaunchKernelGGL((pt_primary_wf<WF_STACK, decltype(tbl)::value>), grid, dim3(WF_TRACE_BLOCK), 0, w, s, fp, pb, primary);
+    };
+    if (int rc = trace_step(c, s, w, (size_t)fp.rows * fp.width, launch)) return rc;
+    have = key;
     return PNRT_OK;
 }
 
 // A pipe's buffers for batches of `slots` path slots and `color_bytes` of frame colours
-// over a shard of `pix` pixels (render_wavefront, render_adaptive).
-static int pipe_size(pnrt_ctx* c, pnrt_ctx::Pipe& Q, size_t pix, size_t color_bytes, size_t slots, size_t ovf_bytes) {
+// over a shard of `pix` pixels of a call of source `src` (start_call).
+static int pipe_size(pnrt_ctx* c, pnrt_ctx::Pipe& Q, const PathSource& src, size_t pix, size_t color_bytes, size_t slots) {
     bool moved = false;
     int rc = Q.primary.reserve(c, pix * 48, &moved);
     if (moved) Q.prim.valid = false;
     if (rc || (rc = Q.colors.reserve(c, color_bytes)) || (rc = Q.wf.reserve(c, wf_bytes(slots) + 512)) ||
-        (rc = Q.ovf.reserve(c, ovf_bytes)))
+        (rc = Q.ovf.reserve(c, ovf_size(c).bytes)) || (rc = Q.camrec.reserve(c, slots * src.slot_bytes())) ||
+        (src.cams && (rc = Q.camtab.reserve(c, (size_t)WF_MAX_CHUNK_FRAMES * 48))))
         return rc;
     return PNRT_OK;
 }
@@ -851,16 +899,12 @@ struct BatchRoute {
     hipStream_t w;           // the stream of the batches' kernels (the caller's for a lone call)
     bool alone, one, stagger;
     int ovf_stride, tiles_x;
-    const WfAdapt* ad;       // an adaptive call's active-tile list, or null
-    const float* cams;       // pnrt_render_cameras: the call's cameras (pinned host memory, 12 floats per frame), or null
-    const float4* rays;      // pnrt_render_rays, pnrt_render_rays_adaptive (with ad): the call's first set (device memory), or null,
-    int64_t ray_stride;      // and the records between the sets of consecutive frames
 };
 // The batches of one call on pipe P: per group of `chunk` frames one batch (gen ->
 // {trace -> shade} x depth) of per_frame path slots per frame on R.w, then the
 // frame-ordered blend on the context stream.
-static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pnrt_ctx::Pipe& P, const BatchRoute& R,
-                       size_t per_frame, uint32_t chunk, uint32_t first, uint32_t nf) {
+static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pnrt_ctx::Pipe& P, const PathSource& src,
+                       const BatchRoute& R, size_t per_frame, uint32_t chunk, uint32_t first, uint32_t nf) {
     int rc;
     const size_t pix = (size_t)fp.rows * c->width;
     hipStream_t w = R.w;
@@ -875,45 +919,31 @@ static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pn
         a.b.first_frame = first + f0;
         if (f0 && w != c->stream) HIPCHK(c, hipStreamWaitEvent(w, P.ev_blend, 0));   // the previous group's blend has read the colours
         const bool last = f0 + cf >= nf;
-        const float4* primary = P.primary;
-        WfCams cm{nullptr};
-        if (R.cams) {
+        const WfCams cm{P.camtab};
+        const WfRays ry{src.rays + 2 * ((size_t)f0 * (size_t)src.ray_stride), src.ray_stride};
+        if (src.kind == PathSource::CAMERAS) {
             // the batch's cameras, then its camera rays: one per path slot (pt_cameras.h).  Both follow
             // the previous batch's kernels on w, the last readers of the table and the records
-            cm.table = P.camtab;
-            primary = P.camrec;
-            HIPCHK(c, hipMemcpyAsync(P.camtab, R.cams + 12 * (size_t)f0, (size_t)cf * 48, hipMemcpyHostToDevice, w));
-            ProfScope ps(c, PNRT_K_PRIMARY, w);
-            const unsigned gp = (unsigned)std::min<size_t>(((size_t)a.b.n + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
-            if (s.has_leaf_table)
-                hipLaunchKernelGGL((pt_camera_rays_wf<WF_STACK, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, cm, P.camrec);
-            else
-                hipLaunchKernelGGL((pt_camera_rays_wf<WF_STACK, false>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, cm, P.camrec);
-            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(P.camtab, src.cams + 12 * (size_t)f0, (size_t)cf * 48, hipMemcpyHostToDevice, w));
+            const auto launch = [&](auto tbl, dim3 grid) {
+                hipLaunchKernelGGL((pt_camera_rays_wf<WF_STACK, decltype(tbl)::value>), grid, dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, cm,
+                                   P.camrec);
+            };
+            if ((rc = trace_step(c, s, w, a.b.n, launch))) return rc;
         }
-        WfRays ry{nullptr, 0};
-        if (R.rays) {
-            // the batch's camera rays from the caller's sets f0 .. f0 + cf - 1: one per path slot (pt_rays.h), behind the
-            // previous batch's kernels on w, the last readers of the records
-            ry.rays = R.rays + 2 * ((size_t)f0 * (size_t)R.ray_stride);
-            ry.frame_stride = R.ray_stride;
-            primary = P.camrec;
-            ProfScope ps(c, PNRT_K_PRIMARY, w);
-            const unsigned gp = (unsigned)std::min<size_t>(((size_t)a.b.n + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
-            if (R.ad && s.has_leaf_table)     // (an adaptive call's: the list's slots)
-                hipLaunchKernelGGL((pt_rays_wf<WF_STACK, true, false, WfAdapt>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, ry,
-                                   P.camrec, *R.ad);
-            else if (R.ad)
-                hipLaunchKernelGGL((pt_rays_wf<WF_STACK, false, false, WfAdapt>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, ry,
-                                   P.camrec, *R.ad);
-            else if (s.has_leaf_table)
-                hipLaunchKernelGGL((pt_rays_wf<WF_STACK, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, ry, P.camrec);
-            else
-                hipLaunchKernelGGL((pt_rays_wf<WF_STACK, false>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, w, s, fp, a.b, ry, P.camrec);
-            HIPCHK(c, hipGetLastError());
+        if (src.kind == PathSource::RAYS) {
+            // the batch's camera rays from the caller's sets f0 .. f0 + cf - 1: one per path slot (pt_rays.h; an
+            // adaptive call's: the list's slots), behind the previous batch's kernels on w, the last readers of the records
+            const auto launch = [&](auto tbl, dim3 grid) {
+                src.with_tiles([&](auto... ad) {
+                    hipLaunchKernelGGL((pt_rays_wf<WF_STACK, decltype(tbl)::value, false, decltype(ad)...>), grid, dim3(WF_TRACE_BLOCK),
+                                       0, w, s, fp, a.b, ry, P.camrec, ad...);
+                });
+            };
+            if ((rc = trace_step(c, s, w, a.b.n, launch))) return rc;
         }
-        if ((rc = render_batch(c, s, fp, a, w, primary, P.colors, R.alone, R.one, R.stagger && last ? P.ev_stage : nullptr,
-                               R.ad, R.cams ? &cm : nullptr, R.rays ? &ry : nullptr)))
+        if ((rc = render_batch(c, s, fp, a, w, src.per_pixel_records() ? P.primary : P.camrec, P.colors, R.alone, R.one,
+                               R.stagger && last ? P.ev_stage : nullptr, src, cm, ry)))
             return rc;
         if (R.stagger && last) P.stage_set = true;
         if (w != c->stream) {
@@ -922,9 +952,9 @@ static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pn
         }
         {   // the blends run in call order on the caller's stream
             ProfScope ps(c, PNRT_K_BLEND);
-            if (R.ad)                   // the active pixels' blend and moments (pt_adaptive.h)
-                hipLaunchKernelGGL(pt_blend_adaptive_kernel, dim3((unsigned)(((size_t)R.ad->n_tiles * 64 + 255) / 256)), dim3(256),
-                                   0, c->stream, fp, *R.ad, R.tiles_x, (const float4*)P.colors, c->accum, c->moments, (int)cf,
+            if (src.tiles)              // the active pixels' blend and moments (pt_adaptive.h)
+                hipLaunchKernelGGL(pt_blend_adaptive_kernel, dim3((unsigned)(((size_t)src.tiles->n_tiles * 64 + 255) / 256)), dim3(256),
+                                   0, c->stream, fp, *src.tiles, R.tiles_x, (const float4*)P.colors, c->accum, c->moments, (int)cf,
                                    first + f0);
             else if (c->moments_on)     // the same blend, and the moments of the batch's frames (pt_moments.h)
                 hipLaunchKernelGGL(pt_blend_moments_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, fp,
@@ -941,25 +971,72 @@ static int run_batches(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, pn
     return PNRT_OK;
 }
 
+// What render_wavefront and render_adaptive decide about a call before it starts on its pipe.
+struct CallShape {
+    unsigned pipe, prev_pipe;        // the call's pipe; the pipe of the call before it
+    unsigned npipes;                 // the pipes sized now: the ones this call size rotates over, from `pipe` on
+    size_t per_frame, color_bytes;   // path slots per frame; a batch's colours
+    uint32_t chunk;                  // frames per batch
+    bool alone, one, stagger;
+};
+// Start a call of source `src` on its pipe: the buffers, the order against what used them last (and, for a
+// source that reads the caller's memory, against the context stream), the pipe's primary records where the
+// source uses them, the batches.
+static int start_call(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const PathSource& src, const CallShape& k,
+                      uint32_t first, uint32_t nf) {
+    int rc;
+    pnrt_ctx::Pipe& P = c->pipe[k.pipe];
+    // every buffer set this call size rotates over is sized now, so no later call of
+    // the same size reallocates (a reallocation waits for all calls in flight)
+    for (unsigned q = 0; q < k.npipes; ++q)
+        if ((rc = pipe_size(c, c->pipe[q ? (k.pipe + q) % k.npipes : k.pipe], src, (size_t)fp.rows * c->width, k.color_bytes,
+                            k.per_frame * k.chunk)))
+            return rc;
+    ++c->ncall;
+    // A call with nothing in flight runs on the caller's stream itself: no worker
+    // stream to order against it, so no event wait before its first kernel and no
+    // join before its blend (the reference's loop: one frame, then display)
+    const bool on_caller = k.alone && WF_ALONE_ON_CALLER;
+    hipStream_t w = on_caller ? c->stream : P.w;
+    // this pipe's buffers were last read by the blend of the call that used it last
+    // (already complete for a call with nothing in flight: `alone` queried it)
+    if (P.blend_pending && !k.alone) HIPCHK(c, hipStreamWaitEvent(w, P.ev_blend, 0));
+    // staggered calls: this one starts when the previous one reaches its last bounces
+    if (k.stagger && !k.alone && k.prev_pipe != k.pipe && k.prev_pipe < WF_PIPES && c->pipe[k.prev_pipe].stage_set)
+        HIPCHK(c, hipStreamWaitEvent(w, c->pipe[k.prev_pipe].ev_stage, 0));
+    P.stage_set = false;
+    // the pipe's primary records: traced now, or still valid from an earlier call (PrimKey)
+    if (src.per_pixel_records() && (rc = ensure_primary(c, s, fp, w, P.ovf, P.primary, P.prim))) return rc;
+    if (src.after_caller_stream() && w != c->stream) {   // the caller's writes of the rays, queued on the context stream, before the worker's reads
+        HIPCHK(c, hipEventRecord(P.ev_rays, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(w, P.ev_rays, 0));
+    }
+    const BatchRoute R = {w, k.alone, k.one, k.stagger, ovf_size(c).stride, (c->width + 7) / 8};
+    if ((rc = run_batches(c, s, fp, P, src, R, k.per_frame, k.chunk, first, nf))) return rc;
+    if (src.cams) {             // behind the call's last table copy: the staging block is free once it completes
+        pnrt_ctx::CamStage& S = c->cam_stage.back();
+        HIPCHK(c, hipEventRecord(S.ev, w));
+        S.pending = true;
+    }
+    return PNRT_OK;
+}
+
 // v3 wavefront, one pnrt_render call on a pipe: the primary pass (unless the
 // pipe's records are still valid, PrimKey), then per group of <= WF_MAX_CHUNK_FRAMES frames one
 // batch (gen -> {trace -> shade} x depth) on the pipe's worker stream, then the
 // frame-ordered blend on the context stream.  Consecutive calls are independent
 // path sets, so running them concurrently changes nothing in the result; the
 // blends keep frame order.
-// cams: pnrt_render_cameras' call -- the cameras of its nf frames in pinned host memory; the batches
-// are planned with the camera-ray records' bytes, trace their own camera rays (run_batches) and
-// leave the pipe's per-pixel records and their key alone.
-// rays: pnrt_render_rays' call -- the caller's device ray sets, ray_stride records apart; planned and
-// buffered like a camera call, and every batch's reads follow what the context stream held at the call.
-static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, uint32_t first, uint32_t nf,
-                            const float* cams = nullptr, const float4* rays = nullptr, int64_t ray_stride = 0) {
+// A camera call (pnrt_render_cameras) or a ray call (pnrt_render_rays) is planned with its camera-ray
+// records' bytes; its batches trace their own camera rays (run_batches) and leave the pipe's per-pixel
+// records and their key alone.
+static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const PathSource& src, uint32_t first,
+                            uint32_t nf) {
     int rc;
     if ((rc = pipes_init(c))) return rc;
     const size_t pix = (size_t)fp.rows * c->width;
-    const int tiles_x = (c->width + 7) / 8;
     const size_t per_frame = frame_paths(c->width, fp.rows);
-    const uint32_t chunk = plan_chunk(c, per_frame, pix, nf, cams || rays ? CAM_REC_BYTES : 0);   // frames per batch
+    const uint32_t chunk = plan_chunk(c, per_frame, pix, nf, src.slot_bytes());   // frames per batch
     if (chunk == 0) return set_err(c, PNRT_E_ARG, "render: frame too large for one batch");
     // calls in flight by call size (paths per batch): small (< 5M: multi-GPU shares)
     // 4 with > 4 hardware queues; 5M-12M 2 -- their launches are long enough to fill
@@ -990,76 +1067,22 @@ static int render_wavefront(pnrt_ctx* c, const DevScene& s, const FrameParams& f
     const unsigned pi = (alone && c->last_pipe < npipes) ? c->last_pipe : c->next_pipe % npipes;
     c->next_pipe = (pi + 1) % npipes;
     c->last_pipe = pi;
-    pnrt_ctx::Pipe& P = c->pipe[pi];
     if ((rc = trace_grid_init(c))) return rc;
-    const OvfSize ovf = ovf_size(c);
-    // every buffer set this call size rotates over is sized now, so no later call of
-    // the same size reallocates (a reallocation waits for all calls in flight)
-    for (unsigned q = 0; q < npipes; ++q)
-        if ((rc = pipe_size(c, c->pipe[(pi + q) % npipes], pix, pix * 16 * chunk, per_frame * chunk, ovf.bytes))) return rc;
-    if (cams || rays)
-        for (unsigned q = 0; q < npipes; ++q) {
-            pnrt_ctx::Pipe& Q = c->pipe[(pi + q) % npipes];
-            if ((rc = Q.camrec.reserve(c, per_frame * chunk * CAM_REC_BYTES)) ||
-                (cams && (rc = Q.camtab.reserve(c, (size_t)WF_MAX_CHUNK_FRAMES * 48))))
-                return rc;
-        }
-    ++c->ncall;
-    // A call with nothing in flight runs on the caller's stream itself: no worker
-    // stream to order against it, so no event wait before its first kernel and no
-    // join before its blend (the reference's loop: one frame, then display)
-    const bool on_caller = alone && WF_ALONE_ON_CALLER;
-    hipStream_t w = on_caller ? c->stream : P.w;
-    // this pipe's buffers were last read by the blend of the call that used it last
-    // (already complete for a call with nothing in flight: `alone` queried it)
-    if (P.blend_pending && !alone) HIPCHK(c, hipStreamWaitEvent(w, P.ev_blend, 0));
-    // staggered calls: this one starts when the previous one reaches its last bounces
-    if (stagger && !alone && prev_pipe != pi && prev_pipe < WF_PIPES && c->pipe[prev_pipe].stage_set)
-        HIPCHK(c, hipStreamWaitEvent(w, c->pipe[prev_pipe].ev_stage, 0));
-    P.stage_set = false;
-    // the pipe's primary records: traced now, or still valid from an earlier call (PrimKey)
-    if (!cams && !rays && (rc = ensure_primary(c, s, fp, w, P.ovf, ovf.stride, P.primary, P.prim))) return rc;
-    if (rays && w != c->stream) {   // the caller's writes of the rays, queued on the context stream, before the worker's reads
-        HIPCHK(c, hipEventRecord(P.ev_rays, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(w, P.ev_rays, 0));
-    }
-    const BatchRoute R = {w, alone, one, stagger, ovf.stride, tiles_x, nullptr, cams, rays, ray_stride};
-    if ((rc = run_batches(c, s, fp, P, R, per_frame, chunk, first, nf))) return rc;
-    if (cams) {                 // behind the call's last table copy: the staging block is free once it completes
-        pnrt_ctx::CamStage& S = c->cam_stage.back();
-        HIPCHK(c, hipEventRecord(S.ev, w));
-        S.pending = true;
-    }
-    return PNRT_OK;
+    return start_call(c, s, fp, src, {pi, prev_pipe, npipes, per_frame, pix * 16 * chunk, chunk, alone, one, stagger}, first, nf);
 }
 
 // pnrt_render_adaptive's frames: the batches over the active tiles' path slots.  The
 // call has waited for everything in flight, so it is a lone call: the last call's pipe
-// (its primary records likely still valid, PrimKey), the caller's stream.
-// rays: pnrt_render_rays_adaptive's call -- the caller's sets as render_wavefront takes them; the batches trace
-// the list's camera rays into the pipe's per-slot records and leave its per-pixel ones and their key alone.
-static int render_adaptive(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const WfAdapt& ad, uint32_t chunk,
-                           uint32_t first, uint32_t nf, const float4* rays = nullptr, int64_t ray_stride = 0) {
+// (its primary records likely still valid, PrimKey) with no rotation, the caller's stream.
+// (pnrt_render_rays_adaptive's: the batches trace the list's camera rays into the pipe's per-slot records.)
+static int render_adaptive(pnrt_ctx* c, const DevScene& s, const FrameParams& fp, const PathSource& src, uint32_t chunk,
+                           uint32_t first, uint32_t nf) {
     int rc;
     if ((rc = pipes_init(c)) || (rc = trace_grid_init(c))) return rc;
-    const size_t pix = (size_t)fp.rows * c->width;
-    const size_t per_frame = (size_t)ad.n_tiles * 64;
-    const bool alone = !c->serial;
-    pnrt_ctx::Pipe& P = c->pipe[c->last_pipe < c->n_pipes_small ? c->last_pipe : 0];
-    c->last_pipe = (unsigned)(&P - c->pipe);
-    const OvfSize ovf = ovf_size(c);
-    if ((rc = pipe_size(c, P, pix, per_frame * 16 * chunk, per_frame * chunk, ovf.bytes))) return rc;
-    if (rays && (rc = P.camrec.reserve(c, per_frame * chunk * CAM_REC_BYTES))) return rc;
-    ++c->ncall;
-    hipStream_t w = (alone && WF_ALONE_ON_CALLER) ? c->stream : P.w;
-    P.stage_set = false;
-    if (!rays && (rc = ensure_primary(c, s, fp, w, P.ovf, ovf.stride, P.primary, P.prim))) return rc;
-    if (rays && w != c->stream) {   // (render_wavefront's order: the caller's writes of the rays before the worker's reads)
-        HIPCHK(c, hipEventRecord(P.ev_rays, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(w, P.ev_rays, 0));
-    }
-    const BatchRoute R = {w, alone, c->serial, false, ovf.stride, (c->width + 7) / 8, &ad, nullptr, rays, ray_stride};
-    return run_batches(c, s, fp, P, R, per_frame, chunk, first, nf);
+    const size_t per_frame = (size_t)src.tiles->n_tiles * 64;
+    const unsigned pi = c->last_pipe < c->n_pipes_small ? c->last_pipe : 0;
+    c->last_pipe = pi;
+    return start_call(c, s, fp, src, {pi, pi, 1, per_frame, per_frame * 16 * chunk, chunk, !c->serial, c->serial, false}, first, nf);
 }
 
 // The scene as the kernels take it: the uploaded arrays with the environment,
@@ -1104,14 +1127,17 @@ static bool guide_key_eq(const pnrt_ctx::GuideKey& a, const pnrt_ctx::GuideKey& 
 }
 
 // The guide images of camera `cam` (the current one for pnrt_render_guides; the one the
-// accumulation was rendered with, then the current one, for pnrt_reproject).
-static int render_guides(pnrt_ctx* c, const pnrt_camera& cam) {
+// accumulation was rendered with, then the current one, for pnrt_reproject) or, with `rays`, of one ray
+// set (pnrt_render_guides_rays; both views of pnrt_reproject_view: the camera's floats are not read).
+// A camera's records are lent by a pipe or traced into the guides' own buffer under its key; a set's are
+// traced there, one launch of class PNRT_K_PRIMARY, and have no key.  The checks are the caller's.
+static int render_guides(pnrt_ctx* c, const pnrt_camera& cam, const void* rays) {
     int rc;
     if ((rc = pipes_init(c)) || (rc = trace_grid_init(c))) return rc;
     const DevScene s = launch_scene(c);
     const FrameParams fp = full_frame_params(c, cam);
     const size_t pix = (size_t)c->width * c->height;
-    if (pix > 0xFFFFFFFFull / 64) return set_err(c, PNRT_E_ARG, "render_guides: frame too large");
+    if (pix > 0xFFFFFFFFull / 64) return set_err(c, PNRT_E_ARG, std::string(rays ? "render_guides_rays" : "render_guides") + ": frame too large");
     for (int k = 0; k < PNRT_AOV_COUNT; ++k)
         if ((rc = c->aov[k].reserve(c, pix * 16))) return rc;
     // A pipe that holds the records of the whole image (any band: one shard owns
@@ -1122,27 +1148,34 @@ static int render_guides(pnrt_ctx* c, const pnrt_camera& cam) {
     const pnrt_ctx::PrimKey want = prim_key(c, fp);    // one shard of one band: shard 0 of 1
     pnrt_ctx::Pipe* lender = nullptr;
     for (auto& Q : c->pipe)
-        if (Q.primary && Q.blend_pending && prim_key_eq(Q.prim, want, /* any_band */ true)) {
-            lender = &Q;
-            break;
-        }
-    const float4* rec = nullptr;
-    if (lender) {
-        rec = lender->primary;
-    } else {            // records of the guides' own, in a buffer and a spill area no pipe uses
-        const OvfSize ovf = ovf_size(c);
+        if (!rays && !lender && Q.primary && Q.blend_pending && prim_key_eq(Q.prim, want, /* any_band */ true)) lender = &Q;
+    if (!lender) {      // records of the guides' own, in a buffer and a spill area no pipe uses
         bool moved = false;
         rc = c->g_primary.reserve(c, pix * 48, &moved);
-        if (moved) c->g_prim.valid = false;
-        if (rc || (rc = c->g_ovf.reserve(c, ovf.bytes))) return rc;
-        if ((rc = ensure_primary(c, s, fp, c->stream, c->g_ovf, ovf.stride, c->g_primary, c->g_prim))) return rc;
-        rec = c->g_primary;
+        if (moved || rays) c->g_prim.valid = false;
+        if (rc || (rc = c->g_ovf.reserve(c, ovf_size(c).bytes))) return rc;
+        if (rays) {
+            WfBufs pb = spill_bufs(c, c->g_ovf);
+            pb.n = (uint32_t)frame_paths(c->width, c->height);       // one frame's slots: wf_coords' tiles
+            pb.chunk_frames = 1;
+            pb.tiles_x = (c->width + 7) / 8;
+            const WfRays ry{static_cast<const float4*>(rays), 0};
+            const auto launch = [&](auto tbl, dim3 grid) {
+                hipLaunchKernelGGL((pt_rays_wf<WF_STACK, decltype(tbl)::value, true>), grid, dim3(WF_TRACE_BLOCK), 0, c->stream, s, fp,
+                                   pb, ry, c->g_primary.p);
+            };
+            if ((rc = trace_step(c, s, c->stream, pb.n, launch))) return rc;
+        } else if ((rc = ensure_primary(c, s, fp, c->stream, c->g_ovf, c->g_primary, c->g_prim))) {
+            return rc;
+        }
     }
+    const float4* rec = lender ? lender->primary : c->g_primary;
     hipLaunchKernelGGL(pt_guides, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, s, rec,
                        c->aov[PNRT_AOV_POSITION], c->aov[PNRT_AOV_NORMAL], c->aov[PNRT_AOV_ALBEDO], (uint32_t)pix);
     HIPCHK(c, hipGetLastError());
     if (lender) HIPCHK(c, hipEventRecord(lender->ev_blend, c->stream));
     c->guide_key = guide_key_for(c, cam);
+    c->guide_key.rays = rays != nullptr;
     return mark_stream(c);
 }
 
@@ -1158,25 +1191,17 @@ static int query_launch(pnrt_ctx* c, const float* rays, int64_t n, int kind, uin
     int rc;
     if ((rc = trace_grid_init(c))) return rc;
     const DevScene s = launch_scene(c);
-    const OvfSize ovf = ovf_size(c);
-    if ((rc = c->q_ovf.reserve(c, ovf.bytes))) return rc;
-    WfBufs qb{};
-    qb.ovf = c->q_ovf;
-    qb.fault = c->fault_dev;
-    qb.ovf_stride = (uint32_t)ovf.stride;
+    if ((rc = c->q_ovf.reserve(c, ovf_size(c).bytes))) return rc;
+    const WfBufs qb = spill_bufs(c, c->q_ovf);
     const int mode = traverse_mode(c);
     const int any = kind == PNRT_QUERY_ANY;
     for (int64_t at = 0; at < n; at += QUERY_MAX_LAUNCH) {
         const uint32_t m = (uint32_t)std::min<int64_t>(n - at, QUERY_MAX_LAUNCH);
-        ProfScope ps(c, PNRT_K_PRIMARY, c->stream);
-        const unsigned g = (unsigned)std::min<size_t>(((size_t)m + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
-        if (s.has_leaf_table)
-            hipLaunchKernelGGL((pt_query_wf<WF_STACK, true>), dim3(g), dim3(WF_TRACE_BLOCK), 0, c->stream, s, qb, rays + 7 * at, m,
-                               any, mode, out + 4 * at);
-        else
-            hipLaunchKernelGGL((pt_query_wf<WF_STACK, false>), dim3(g), dim3(WF_TRACE_BLOCK), 0, c->stream, s, qb, rays + 7 * at, m,
-                               any, mode, out + 4 * at);
-        HIPCHK(c, hipGetLastError());
+        const auto launch = [&](auto tbl, dim3 grid) {
+            hipLaunchKernelGGL((pt_query_wf<WF_STACK, decltype(tbl)::value>), grid, dim3(WF_TRACE_BLOCK), 0, c->stream, s, qb,
+                               rays + 7 * at, m, any, mode, out + 4 * at);
+        };
+        if ((rc = trace_step(c, s, c->stream, m, launch))) return rc;
     }
     return mark_stream(c);
 }
@@ -1295,6 +1320,21 @@ static int need_moments(pnrt_ctx* c, const char* who) {
         return set_err(c, PNRT_E_STATE, std::string(who) + ": frames were rendered while the moments were disabled, so they do not "
                                               "cover the accumulation (pnrt_reset_accum first)");
     return PNRT_OK;
+}
+
+// The stretch the frame-rendering entry points share once their arguments have passed: the faults of
+// completed work, then the call's frame parameters and the scene as its kernels take it.  A call of no
+// frames, or whose shard has no rows, queues nothing (each entry point returns there in its own way).
+static int frame_call(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int shard, FrameParams* fp, DevScene* s) {
+    if (int rc = check_fault(c)) return rc;      // an earlier call's trace fault (completed work)
+    if (nf) HIPCHK(c, hipSetDevice(c->device));
+    *fp = frame_params(c, c->cam, first, nf, band, nsh, shard);
+    *s = launch_scene(c);
+    return PNRT_OK;
+}
+// frames the sample moments do not count (pnrt_render_adaptive refuses from then on)
+static void moments_uncover(pnrt_ctx* c) {
+    if (!c->moments_on) c->mom_cover = false;
 }
 
 // The tail of the pnrt_read_* calls: `bytes` of a device image to the caller behind everything
@@ -2115,13 +2155,12 @@ int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int
     // the one-kernel path keeps its frames in registers: no per-frame colours to take moments of
     if (c->kernel == 1 && c->moments_on)
         return set_err(c, PNRT_E_STATE, "render: PNRT_KERNEL_V1 cannot update the sample moments (pnrt_enable_moments(ctx, 0) first)");
-    if (int rc = check_fault(c)) return rc;      // an earlier call's trace fault (completed work)
+    FrameParams fp;
+    DevScene s;
+    if (int rc = frame_call(c, first, nf, band, nsh, shard, &fp, &s)) return rc;
     if (nf == 0) return PNRT_OK;
-    if (!c->moments_on) c->mom_cover = false;    // frames the moments do not count (pnrt_render_adaptive)
-    HIPCHK(c, hipSetDevice(c->device));
-    const FrameParams fp = frame_params(c, c->cam, first, nf, band, nsh, shard);
+    moments_uncover(c);                          // (here before the shard's rows are known, unlike the other entry points)
     if (fp.rows == 0) return PNRT_OK;
-    DevScene s = launch_scene(c);
     if (WF_DIAG_BOUNDS) {                // the bounds check's own test (diagnostic builds only)
         const char* f = getenv("PNRT_DIAG_FORCE_OOB");
         s.diag_force = (f && atoi(f) > 0) ? 1 : 0;
@@ -2135,7 +2174,7 @@ int pnrt_render(pnrt_ctx* c, uint32_t first, uint32_t nf, int band, int nsh, int
         HIPCHK(c, hipGetLastError());
         return mark_stream(c);           // (every op queued on c->stream records ev_last)
     }
-    return render_wavefront(c, s, fp, first, nf);
+    return render_wavefront(c, s, fp, PathSource::records(), first, nf);
 }
 
 // A staging block for a call's cameras, moved to the back of the list: one whose last copy has
@@ -2174,21 +2213,19 @@ int pnrt_render_cameras(pnrt_ctx* c, uint32_t first, uint32_t nf, const pnrt_cam
             return set_err(c, PNRT_E_ARG, "render_cameras: a camera component is not finite: frame " +
                                               std::to_string((uint64_t)first + i / 12) + " (cameras[" + std::to_string(i / 12) +
                                               "], float " + std::to_string(i % 12) + ")");
-    if (int rc = check_fault(c)) return rc;      // an earlier call's trace fault (completed work)
-    if (nf == 0) return PNRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const FrameParams fp = frame_params(c, c->cam, first, nf, band, nsh, shard);
-    if (fp.rows == 0) return PNRT_OK;
-    if (!c->moments_on) c->mom_cover = false;    // frames the moments do not count, as pnrt_render's
-    const DevScene s = launch_scene(c);
+    FrameParams fp;
+    DevScene s;
+    if (int rc = frame_call(c, first, nf, band, nsh, shard, &fp, &s)) return rc;
+    if (nf == 0 || fp.rows == 0) return PNRT_OK;
+    moments_uncover(c);
     // the array is the caller's again when this returns: the batches read the copy
     if (int rc = cam_stage_get(c, (size_t)nf * 48)) return rc;
     std::memcpy(c->cam_stage.back().host, cf, (size_t)nf * 48);
-    return render_wavefront(c, s, fp, first, nf, c->cam_stage.back().host);
+    return render_wavefront(c, s, fp, PathSource::cameras(c->cam_stage.back().host), first, nf);
 }
 
-// pnrt_batch_plan / pnrt_cameras_batch_plan: the plan of a call whose paths hold per_path further bytes.
-static int batch_plan(pnrt_ctx* c, const std::string& who, size_t per_path, uint32_t nf, int band, int nsh, int shard,
+// pnrt_batch_plan / pnrt_cameras_batch_plan: the plan of a call of source `src`.
+static int batch_plan(pnrt_ctx* c, const std::string& who, const PathSource& src, uint32_t nf, int band, int nsh, int shard,
                       uint32_t* frames_per_batch, uint32_t* n_batches, int64_t* bytes) {
     if (!c) return PNRT_E_ARG;
     if (!c->has_frame) return set_err(c, PNRT_E_STATE, who + ": set_frame first");
@@ -2198,10 +2235,10 @@ static int batch_plan(pnrt_ctx* c, const std::string& who, size_t per_path, uint
     const int rows = shard_rows(c->height, band, nsh, shard);
     if (nf > 0 && rows > 0) {                    // (the render call queues nothing otherwise)
         const size_t per_frame = frame_paths(c->width, rows), pix = (size_t)rows * c->width;
-        chunk = plan_chunk(c, per_frame, pix, nf, per_path);
+        chunk = plan_chunk(c, per_frame, pix, nf, src.slot_bytes());
         if (chunk == 0) return set_err(c, PNRT_E_ARG, who + ": frame too large for one batch");
         nb = nf / chunk + (nf % chunk ? 1u : 0u);
-        by = (int64_t)batch_bytes(per_frame, pix, chunk, per_path);
+        by = (int64_t)batch_bytes(per_frame, pix, chunk, src.slot_bytes());
     }
     if (frames_per_batch) *frames_per_batch = chunk;
     if (n_batches) *n_batches = nb;
@@ -2211,12 +2248,12 @@ static int batch_plan(pnrt_ctx* c, const std::string& who, size_t per_path, uint
 
 int pnrt_cameras_batch_plan(pnrt_ctx* c, uint32_t nf, int band, int nsh, int shard, uint32_t* frames_per_batch,
                             uint32_t* n_batches, int64_t* bytes) {
-    return batch_plan(c, "cameras_batch_plan", CAM_REC_BYTES, nf, band, nsh, shard, frames_per_batch, n_batches, bytes);
+    return batch_plan(c, "cameras_batch_plan", PathSource::cameras(nullptr), nf, band, nsh, shard, frames_per_batch, n_batches, bytes);
 }
 
 int pnrt_batch_plan(pnrt_ctx* c, uint32_t nf, int band, int nsh, int shard, uint32_t* frames_per_batch,
                     uint32_t* n_batches, int64_t* bytes) {
-    return batch_plan(c, "batch_plan", 0, nf, band, nsh, shard, frames_per_batch, n_batches, bytes);
+    return batch_plan(c, "batch_plan", PathSource::records(), nf, band, nsh, shard, frames_per_batch, n_batches, bytes);
 }
 
 int pnrt_reset_accum(pnrt_ctx* c) {
@@ -2254,7 +2291,7 @@ int pnrt_render_guides(pnrt_ctx* c) {
     if (int rc = need_scene_frame(c, "render_guides")) return rc;
     if (int rc = check_fault(c)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    return render_guides(c, c->cam);
+    return render_guides(c, c->cam, nullptr);
 }
 
 // ---- caller ray buffers (pt_rays.h) -------------------------------------
@@ -2281,56 +2318,12 @@ int pnrt_render_rays(pnrt_ctx* c, uint32_t first, uint32_t nf, const void* rays,
     if (int rc = check_selector(c, "render_rays", band, nsh, shard)) return rc;
     if (int rc = check_frame_range(c, "render_rays", first, nf)) return rc;
     if (int rc = check_ray_buffer(c, "render_rays", rays, stride, nf)) return rc;
-    if (int rc = check_fault(c)) return rc;      // an earlier call's trace fault (completed work)
-    if (nf == 0) return PNRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const FrameParams fp = frame_params(c, c->cam, first, nf, band, nsh, shard);
-    if (fp.rows == 0) return PNRT_OK;
-    if (!c->moments_on) c->mom_cover = false;    // frames the moments do not count, as pnrt_render's
-    const DevScene s = launch_scene(c);
-    return render_wavefront(c, s, fp, first, nf, nullptr, static_cast<const float4*>(rays), stride);
-}
-
-// The guide images of one ray set (pnrt_render_guides_rays; both views of pnrt_reproject_view): one trace of
-// class PNRT_K_PRIMARY into the guides' own record buffer, then pt_guides.  The checks are the caller's.
-static int render_guides_rays(pnrt_ctx* c, const void* rays) {
-    int rc;
-    if ((rc = pipes_init(c)) || (rc = trace_grid_init(c))) return rc;
-    const DevScene s = launch_scene(c);
-    const FrameParams fp = full_frame_params(c, c->cam);     // (the camera floats are not read)
-    const size_t pix = (size_t)c->width * c->height;
-    if (pix > 0xFFFFFFFFull / 64) return set_err(c, PNRT_E_ARG, "render_guides_rays: frame too large");
-    for (int k = 0; k < PNRT_AOV_COUNT; ++k)
-        if ((rc = c->aov[k].reserve(c, pix * 16))) return rc;
-    // the guides' own record buffer and spill area (render_guides), whatever they held
-    const OvfSize ovf = ovf_size(c);
-    if ((rc = c->g_primary.reserve(c, pix * 48)) || (rc = c->g_ovf.reserve(c, ovf.bytes))) return rc;
-    c->g_prim.valid = false;
-    WfBufs pb{};
-    pb.ovf = c->g_ovf;
-    pb.fault = c->fault_dev;
-    pb.ovf_stride = (uint32_t)ovf.stride;
-    pb.n = (uint32_t)frame_paths(c->width, c->height);       // one frame's slots: wf_coords' tiles
-    pb.chunk_frames = 1;
-    pb.tiles_x = (c->width + 7) / 8;
-    const WfRays ry{static_cast<const float4*>(rays), 0};
-    {
-        ProfScope ps(c, PNRT_K_PRIMARY, c->stream);
-        const unsigned gp = (unsigned)std::min<size_t>(((size_t)pb.n + WF_TRACE_BLOCK - 1) / WF_TRACE_BLOCK, (size_t)c->trace_grid);
-        if (s.has_leaf_table)
-            hipLaunchKernelGGL((pt_rays_wf<WF_STACK, true, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, c->stream, s, fp, pb, ry,
-                               c->g_primary.p);
-        else
-            hipLaunchKernelGGL((pt_rays_wf<WF_STACK, false, true>), dim3(gp), dim3(WF_TRACE_BLOCK), 0, c->stream, s, fp, pb, ry,
-                               c->g_primary.p);
-    }
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(pt_guides, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, s, (const float4*)c->g_primary,
-                       c->aov[PNRT_AOV_POSITION], c->aov[PNRT_AOV_NORMAL], c->aov[PNRT_AOV_ALBEDO], (uint32_t)pix);
-    HIPCHK(c, hipGetLastError());
-    c->guide_key = guide_key_for(c, c->cam);
-    c->guide_key.rays = true;
-    return mark_stream(c);
+    FrameParams fp;
+    DevScene s;
+    if (int rc = frame_call(c, first, nf, band, nsh, shard, &fp, &s)) return rc;
+    if (nf == 0 || fp.rows == 0) return PNRT_OK;
+    moments_uncover(c);
+    return render_wavefront(c, s, fp, PathSource::ray_sets(rays, stride), first, nf);
 }
 
 int pnrt_render_guides_rays(pnrt_ctx* c, const void* rays) {
@@ -2339,7 +2332,7 @@ int pnrt_render_guides_rays(pnrt_ctx* c, const void* rays) {
     if (int rc = check_ray_buffer(c, "render_guides_rays", rays, 0)) return rc;
     if (int rc = check_fault(c)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    return render_guides_rays(c, rays);
+    return render_guides(c, c->cam, rays);
 }
 
 // pnrt_make_rays' rules for its camera (`who`: the call, or the call and which of its views)
@@ -2577,9 +2570,10 @@ static int adaptive_call(pnrt_ctx* c, const char* who, uint32_t first, uint32_t 
     if (c->kernel == 1) return set_err(c, PNRT_E_STATE, std::string(who) + ": PNRT_KERNEL_V1 has no per-frame colours");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sync_all(c));                      // the predicate reads the moments as every earlier call left them
-    if (int rc = check_fault(c)) return rc;
+    FrameParams fp;
+    DevScene s;
+    if (int rc = frame_call(c, first, nf, band, nsh, shard, &fp, &s)) return rc;
     pnrt_adaptive_stats st{};
-    const FrameParams fp = frame_params(c, c->cam, first, nf, band, nsh, shard);
     const int tiles_x = (c->width + 7) / 8;
     const size_t n_tiles = (size_t)tiles_x * (size_t)((fp.rows + 7) / 8);
     st.n_pixels = (int64_t)fp.rows * c->width;
@@ -2616,20 +2610,20 @@ static int adaptive_call(pnrt_ctx* c, const char* who, uint32_t first, uint32_t 
         ad.tiles = c->ad_list;
         ad.n_tiles = cnt.n_active_tiles;
     }
+    const PathSource src = rays ? PathSource::ray_sets(ray_buf, ray_stride, &ad) : PathSource::records(&ad);
     uint32_t chunk = 0;
     if (nf > 0 && ad.n_tiles > 0) {
         // the plan runs on the active tiles' slots: the colours are compact, 16 bytes per slot (a ray call's slots
         // hold their camera-ray records besides)
         const size_t per_frame = (size_t)ad.n_tiles * 64;
-        chunk = plan_chunk(c, per_frame, per_frame, nf, rays ? CAM_REC_BYTES : 0);
+        chunk = plan_chunk(c, per_frame, per_frame, nf, src.slot_bytes());
         if (chunk == 0) return set_err(c, PNRT_E_ARG, std::string(who) + ": frame too large for one batch");
         st.frames_per_batch = chunk;
         st.n_batches = nf / chunk + (nf % chunk ? 1u : 0u);
     }
     if (out) *out = st;
     if (chunk == 0) return PNRT_OK;              // nothing to render: nothing queued
-    DevScene s = launch_scene(c);
-    return render_adaptive(c, s, fp, ad, chunk, first, nf, static_cast<const float4*>(ray_buf), ray_stride);
+    return render_adaptive(c, s, fp, src, chunk, first, nf);
 }
 
 int pnrt_render_adaptive(pnrt_ctx* c, uint32_t first, uint32_t nf, float threshold, uint32_t min_frames, int band, int nsh,
@@ -2766,9 +2760,9 @@ int pnrt_reproject(pnrt_ctx* c, const pnrt_camera* from, const pnrt_reproject_pa
     if ((rc = reproject_begin(c))) return rc;
     // the guide images of `from` (the current ones when they were rendered for it), kept as the history
     if (!guide_key_eq(c->guide_key, guide_key_for(c, *from), /* camera_keyed */ true))
-        if ((rc = render_guides(c, *from))) return rc;
+        if ((rc = render_guides(c, *from, nullptr))) return rc;
     if ((rc = reproject_keep_history(c))) return rc;
-    if ((rc = render_guides(c, c->cam))) return rc;
+    if ((rc = render_guides(c, c->cam, nullptr))) return rc;
     return reproject_run(c, p, PNRT_CAM_PINHOLE, *from, 0.0f, out);
 }
 
@@ -2786,7 +2780,7 @@ static int reproject_view_guides(pnrt_ctx* c, const pnrt_ray_camera& view) {
         hipLaunchKernelGGL(pt_make_rays_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, c->stream, m, c->rp_rays.p);
     }
     HIPCHK(c, hipGetLastError());
-    return render_guides_rays(c, c->rp_rays.p);
+    return render_guides(c, c->cam, c->rp_rays.p);
 }
 
 int pnrt_reproject_view(pnrt_ctx* c, const pnrt_ray_camera* from, const pnrt_ray_camera* to, const pnrt_reproject_params* params,

@@ -53,10 +53,14 @@ def test_device_deps_and_the_abi_caller():
     assert "c_abi_rays_adaptive.c" in build.ABI_CALLERS and callable(build.build_rays_adaptive_abi_caller)
     wf = open(os.path.join(build.CSRC, "pt_wf.h")).read()
     assert "wf_coords_adaptive_wave" in wf and "wf_pack_get" in wf
-    dev = open(os.path.join(build.CSRC, "pnrt_device.hip")).read()
-    for inst in ("pt_wf_gen_setup<WfAdapt, WfRays>", "pt_wf_shade_setup<true, WfAdapt, WfRays>", "pt_wf_shade_setup<false, WfAdapt, WfRays>",
-                 "pt_rays_wf<WF_STACK, true, false, WfAdapt>", "pt_rays_wf<WF_STACK, false, false, WfAdapt>"):
-        assert inst in dev, inst
+    # the built library holds the call's instantiations (the host code names them through one dispatch, so its text does
+    # not spell them): pt_wf_gen_setup<WfAdapt, WfRays>, pt_wf_shade_setup<true / false, WfAdapt, WfRays>,
+    # pt_rays_wf<WF_STACK, true / false, false, WfAdapt>, by their mangled names
+    N.device_lib()
+    lib = open(N.DEVICE_LIB, "rb").read()
+    for inst in (rb"pt_wf_gen_setupIJ7WfAdapt6WfRaysEE", rb"pt_wf_shade_setupILb1EJ7WfAdapt6WfRaysEE", rb"pt_wf_shade_setupILb0EJ7WfAdapt6WfRaysEE",
+                 rb"pt_rays_wfILi\d+ELb1ELb0EJ7WfAdaptEE", rb"pt_rays_wfILi\d+ELb0ELb0EJ7WfAdaptEE"):
+        assert re.search(inst, lib), inst
 
 
 def test_python_layer_has_the_methods():
