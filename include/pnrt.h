@@ -248,10 +248,25 @@ int pnrt_read_env_table(pnrt_ctx* ctx, float* random_hdr_out);
 /* Replaces the per-frame uniforms SCREEN_WIDTH/HEIGHT (main.cpp:389-390),
  * camera.* (main.cpp:606-610) and MAX_BOUNCE_DEPTH (main.cpp:593,599).
  * (Re)allocates a zeroed width*height RGBA32F accumulation image when the
- * size changes. */
+ * size changes -- and, from the first pnrt_enable_moments on, a zeroed moments
+ * image, which then covers the accumulation again.  A call with the size
+ * unchanged touches neither image: a camera move or another depth alone does
+ * not clear the accumulation.  The caller resets it (pnrt_reset_accum) or goes
+ * on, and later frames blend into the old image by their frame numbers (frame 0,
+ * whose weight is 1, overwrites the rows it renders).
+ * The guide images stay what they were rendered for: under another camera or
+ * size pnrt_denoise* refuse them until pnrt_render_guides (the depth does not
+ * enter: a first hit has none), and a call that comes back to the camera and
+ * size they were rendered for, with the scene and the traversal mode unchanged,
+ * makes them current again.  The denoised and the display image keep the size
+ * they were made at; their readers and PNRT_DISPLAY_DENOISED refuse them while
+ * the frame size is another one. */
 int pnrt_set_frame(pnrt_ctx* ctx, int width, int height, const pnrt_camera* camera,
                    int max_bounce_depth);
 
+/* Takes effect with the next call; no image changes.  The traversal mode is part of
+ * what the guide images were rendered for (pnrt_denoise* refuse guides of the other
+ * mode); PNRT_KERNEL_V1 and PNRT_SERIAL are not. */
 int pnrt_set_options(pnrt_ctx* ctx, int options);
 
 /* Replaces glDispatchCompute (main.cpp:613) called once per frame for frames
@@ -478,7 +493,8 @@ int pnrt_get_device_info(pnrt_ctx* ctx, pnrt_device_info* info);
 int pnrt_render_guides(pnrt_ctx* ctx);
 /* Synchronise and copy one guide image, width*height*4 floats (row 0 = bottom), to
  * the host.  PNRT_E_STATE before pnrt_render_guides, or when the frame size has
- * changed since. */
+ * changed since.  Only the size is checked: guide images that a scene edit, a camera
+ * move or a mode change left stale are still handed out, as they were rendered. */
 int pnrt_read_aov(pnrt_ctx* ctx, int which, float* rgba_out);
 /* Device pointer of a guide image (NULL before the first pnrt_render_guides). */
 void* pnrt_aov_device_ptr(pnrt_ctx* ctx, int which);

@@ -846,7 +846,7 @@ static v3 PathTracing(Ctx* c, Interaction isect, v3 V) {
 }
 
 /* ---- main (:975-992) ------------------------------------------------------ */
-static void shade_pixel(Ctx* c, float* px4) {
+static v3 pixel_color(Ctx* c) {
     c->seed = ((uint32_t)c->px * 1973u + (uint32_t)c->py * 9277u + c->frameCount * 26699u) | 1u;
     Ray ray = CameraGetRay(c, (float)c->px / (float)c->f->width, (float)c->py / (float)c->f->height);
     Interaction isect;
@@ -864,7 +864,11 @@ static void shade_pixel(Ctx* c, float* px4) {
         v3 em = GetMaterial(c, isect.materialId).emssive;
         color = add(em, PathTracing(c, isect, neg(ray.dir)));
     }
-    color = V3(clampf(color.x, 0.0f, 1.0f), clampf(color.y, 0.0f, 1.0f), clampf(color.z, 0.0f, 1.0f));
+    return V3(clampf(color.x, 0.0f, 1.0f), clampf(color.y, 0.0f, 1.0f), clampf(color.z, 0.0f, 1.0f));
+}
+
+static void shade_pixel(Ctx* c, float* px4) {
+    const v3 color = pixel_color(c);
     float a = 1.0f / (float)(c->frameCount + 1u);
     px4[0] = mixf(px4[0], color.x, a);
     px4[1] = mixf(px4[1], color.y, a);
@@ -884,11 +888,12 @@ static void stats_add(pno_stats* d, const pno_stats* s) {
     d->prim_tri_tests += s->prim_tri_tests; d->prim_tri_hits += s->prim_tri_hits;
 }
 
-int pno_render(const pno_scene* scene, const pno_frame* frame,
-               uint32_t first_frame, uint32_t n_frames,
-               int y_begin, int y_end, int y_step,
-               float* accum, int threads, pno_stats* stats) {
-    if (!scene || !frame || !accum || y_step <= 0) return -1;
+/* pno_render (colors NULL) and pno_render_colors (accum NULL) */
+static int render_rows(const pno_scene* scene, const pno_frame* frame,
+                       uint32_t first_frame, uint32_t n_frames,
+                       int y_begin, int y_end, int y_step,
+                       float* accum, float* colors, int threads, pno_stats* stats) {
+    if (!scene || !frame || (!accum && !colors) || y_step <= 0) return -1;
     if (frame->width <= 0 || frame->height <= 0) return -2;
     if (frame->max_bounce_depth < 0 || frame->max_bounce_depth > 4) return -3;
     if (scene->n_nodes <= 0) return -4;
@@ -917,10 +922,16 @@ int pno_render(const pno_scene* scene, const pno_frame* frame,
         c.s = scene; c.f = frame; c.st = &per[tid]; c.py = y_begin + ri * y_step; c.sem = 0;
         for (int x = 0; x < frame->width; ++x) {
             c.px = x;
-            float* p = accum + 4 * ((size_t)c.py * frame->width + x);
+            float* p = accum ? accum + 4 * ((size_t)c.py * frame->width + x) : NULL;
             for (uint32_t k = 0; k < n_frames; ++k) {
                 c.frameCount = first_frame + k;
-                shade_pixel(&c, p);
+                if (accum) {
+                    shade_pixel(&c, p);
+                } else {
+                    const v3 col = pixel_color(&c);
+                    float* q = colors + 3 * (((size_t)k * frame->height + c.py) * frame->width + x);
+                    q[0] = col.x; q[1] = col.y; q[2] = col.z;
+                }
                 per[tid].samples++;
             }
         }
@@ -929,6 +940,22 @@ int pno_render(const pno_scene* scene, const pno_frame* frame,
     free(per);
     if (stats) stats_add(stats, &total);
     return total.stack_overflow ? -6 : 0;
+}
+
+int pno_render(const pno_scene* scene, const pno_frame* frame,
+               uint32_t first_frame, uint32_t n_frames,
+               int y_begin, int y_end, int y_step,
+               float* accum, int threads, pno_stats* stats) {
+    if (!accum) return -1;
+    return render_rows(scene, frame, first_frame, n_frames, y_begin, y_end, y_step, accum, NULL, threads, stats);
+}
+
+int pno_render_colors(const pno_scene* scene, const pno_frame* frame,
+                      uint32_t first_frame, uint32_t n_frames,
+                      int y_begin, int y_end, int y_step,
+                      float* colors, int threads, pno_stats* stats) {
+    if (!colors) return -1;
+    return render_rows(scene, frame, first_frame, n_frames, y_begin, y_end, y_step, NULL, colors, threads, stats);
 }
 
 /* ---- pinning hook: the shading functions on caller inputs ------------------ */

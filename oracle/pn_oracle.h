@@ -84,6 +84,14 @@ int pno_render(const pno_scene* scene, const pno_frame* frame,
                int y_begin, int y_end, int y_step,
                float* accum, int threads, pno_stats* stats);
 
+/* The same frames' clamped colours before the blend (:975-987), for the same rows:
+ * colors is n_frames x height x width x 3 floats, frame k of the call first; the rows
+ * outside the selection and the stats' accum_rmw are left alone. */
+int pno_render_colors(const pno_scene* scene, const pno_frame* frame,
+                      uint32_t first_frame, uint32_t n_frames,
+                      int y_begin, int y_end, int y_step,
+                      float* colors, int threads, pno_stats* stats);
+
 /* Evaluate one PN-libm / IEEE primitive over n inputs (math parity test).
  * fn: 0 sin, 1 cos, 2 atan2(a,b), 3 asin, 4 log, 5 pow(a,b), 6 exp2,
  *     7 sqrt, 8 a/b, 9 float(uint32 bits of a), 10 wang_hash(bits of a) */

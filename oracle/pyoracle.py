@@ -89,6 +89,8 @@ def lib():
         L.pno_render.argtypes = [ctypes.POINTER(Scene), ctypes.POINTER(Frame), ctypes.c_uint32, ctypes.c_uint32,
                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                  ctypes.POINTER(Stats)]
+        L.pno_render_colors.restype = ctypes.c_int
+        L.pno_render_colors.argtypes = L.pno_render.argtypes
         L.pno_math_eval.restype = None
         L.pno_math_eval.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.pno_wang_hash.restype = ctypes.c_uint32
@@ -169,6 +171,19 @@ class Oracle:
         if rc != 0:
             raise RuntimeError(f"pno_render failed ({rc})")
         return accum, st.as_dict()
+
+    def render_colors(self, first_frame: int, n_frames: int, rows=None, threads: int = 0, y_step: int = 1):
+        """The clamped colours of frames first..first+n-1 before the blend, for rows [y0, y1)
+        (step y_step): (n_frames, H, W, 3) float32, zero in the other rows; returns (colors, stats dict)."""
+        W, Hh = self.cfg.width, self.cfg.height
+        colors = np.zeros((n_frames, Hh, W, 3), np.float32)
+        y0, y1 = (0, Hh) if rows is None else rows
+        st = Stats()
+        rc = lib().pno_render_colors(ctypes.byref(self.scene), ctypes.byref(self.frame), first_frame, n_frames,
+                                     y0, y1, y_step, colors.ctypes.data, threads, ctypes.byref(st))
+        if rc != 0:
+            raise RuntimeError(f"pno_render_colors failed ({rc})")
+        return colors, st.as_dict()
 
     def shade_eval(self, fn: int, words: np.ndarray) -> np.ndarray:
         """One shading function of the oracle on n records of 32-bit words

@@ -140,3 +140,30 @@ def test_c1_image_fixture_is_current_oracle():
     import make_c1_image
     gold = np.load(os.path.join(os.path.dirname(__file__), "golden", "c1_oracle_image.npz"))
     np.testing.assert_array_equal(make_c1_image.render().view(np.uint32), gold["image"].view(np.uint32))
+
+
+@pytest.mark.parametrize("name", ["c1", "c2wide", "c3"])
+def test_render_colors_are_the_frames_the_render_blends(name):
+    """Oracle.render_colors hands out the clamped colour of any frame: blended by moments_ref.blend, frames
+    0..12 give Oracle.render's accumulation bit for bit, and at frames 0, 1, 3, 7 and 15 the colours are
+    the ones moments_common.anchor derives from single-frame renders."""
+    import moments_ref as R
+    from guides_common import bits, scene
+    from moments_common import ANCHOR_FRAMES, anchor
+    w, h = 13, 9
+    o = pyoracle.Oracle(scene(name, w, h))
+    acc, st = o.render(0, 13)
+    colors, cst = o.render_colors(0, 13)
+    assert colors.shape == (13, h, w, 3) and colors.dtype == np.float32
+    assert (colors >= 0).all() and (colors <= 1).all() and colors.any()
+    assert cst["samples"] == st["samples"] == 13 * w * h and cst["accum_rmw"] == 0 and st["stack_overflow"] == 0
+    replay = R.blend(np.zeros((h, w, 4), np.float32), colors, range(13))
+    assert np.array_equal(bits(replay), bits(acc))
+    # a call that starts later, and rows: the same colours
+    later, _ = o.render_colors(5, 3, rows=(2, 7), y_step=2)
+    assert np.array_equal(bits(later[:, 2:7:2]), bits(colors[5:8, 2:7:2]))
+    assert not later[:, [0, 1, 3, 5, 7, 8]].any()
+    derived, _, _ = anchor(name, w, h)
+    for f, c in zip(ANCHOR_FRAMES, derived):
+        got, _ = o.render_colors(f, 1)
+        assert np.array_equal(bits(got[0]), bits(c)), f"frame {f}"
