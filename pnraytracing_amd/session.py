@@ -16,6 +16,12 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from .host import camera_pixel_ray, camera_sequence, model_matrix, model_records
+from .tracer import PathTracer, PnrtError, decode_hits, exposure_from_histogram
+
+PINHOLE = ("pinhole", 180.0, 0)                      # set_camera_model never called: (model, fov_deg, per_pixel)
+EVERY_PIXEL = (0.0, 0xFFFFFFFF)                      # the (threshold, min_frames) that make every pixel active
+E_STATE = -3                                         # PNRT_E_STATE
 
 
 class CameraState(ctypes.Structure):
@@ -77,8 +83,14 @@ class CameraController:
 class InteractiveSession:
     """main.cpp:573-630 without the window: one ``frame()`` per loop iteration."""
 
-    _model = _guide_rays = _guide_view = _rendered_view = None   # (class defaults: no camera model, guides keyed by the camera)
+    # A session's private state as it starts (here, not in __init__: a session made with __new__ has it too)
+    _rendered_view = None                            # the view of the last call that rendered: (uniforms, model, fov_deg)
     _counts_differ = False                           # reproject_view left pixels with different frame counts
+    _lens = None                                     # set_lens: (aa_width, lens_radius, focus_distance)
+    _model = None                                    # set_camera_model: (model, fov_deg, per_pixel)
+    _rays = None                                     # the ray buffer of the last frame (alive while its call runs)
+    _guide_rays = None                               # the ray buffer of the guide images, and what it was made for:
+    _guide_view = None                               # (camera uniforms, model, fov_deg, size); None: camera-keyed guides
 
     def __init__(self, tracer, width: int, height: int, camera: CameraController, max_bounce_depth: int = 4):
         self.pt = tracer
@@ -86,13 +98,6 @@ class InteractiveSession:
         self.camera = camera
         self.max_bounce_depth = max_bounce_depth
         self.frame_count = 0
-        self._rendered_camera = None                 # uniforms of the last call that rendered (reproject's `from`)
-        self._rendered_view = None                   # ... and its view: (uniforms, model, fov_deg) (reproject_view's `from`)
-        self._lens = None                            # set_lens: (aa_width, lens_radius, focus_distance)
-        self._model = None                           # set_camera_model: (model, fov_deg, per_pixel)
-        self._rays = None                            # the ray buffer of the last frame (alive while its call runs)
-        self._guide_rays = None                      # the ray buffer of the guide images, and what it was made for:
-        self._guide_view = None                      # (camera uniforms, model, fov_deg, size); None: camera-keyed guides
 
     def set_lens(self, aa_width: float = 1.0, lens_radius: float = 0.0, focus_distance: float | None = None):
         """Anti-aliasing and depth of field for the still frames: from now on ``frame()``
@@ -122,27 +127,29 @@ class InteractiveSession:
         change of model).  A redraw stays the reference's depth-1 frame 0 of the pinhole camera when the
         model is pinhole, and is the same frame through the ray path otherwise.  Never
         called, nothing changes."""
-        from . import _native as N_
-        if isinstance(model, str) and model not in N_.CAM_MODELS:
-            raise ValueError(f"unknown camera model {model!r}: one of {N_.CAM_MODELS}")
-        name = model if isinstance(model, str) else N_.CAM_MODELS[int(model)]
+        name = N.CAM_MODELS[PathTracer._enum("camera model", N.CAM_MODELS, model)]
         if name != "pinhole" and self._lens is not None and self._lens[1] > 0:
             raise ValueError("set_camera_model: a lens (set_lens) needs the pinhole model")
         self._model = (name, float(fov_deg), int(bool(per_pixel)))
 
     def _view(self, cam):
         """(uniforms, model, fov_deg): the view the still frames render with camera uniforms ``cam``."""
-        name, fov, _ = self._model if self._model is not None else ("pinhole", 180.0, 0)
+        name, fov, _ = self._model or PINHOLE
         return (cam, name, fov)
+
+    def _set_frame(self, depth: int):
+        """The controller's uniforms, set as the tracer's camera at that bounce depth."""
+        cam = self.camera.uniforms()
+        self.pt.set_frame(self.width, self.height, cam, depth)
+        return cam
 
     def _remember(self, cam):
         """A call rendered (or reprojected into) the view of ``cam``: what the next reprojection starts from."""
-        self._rendered_camera = cam
         self._rendered_view = self._view(cam)
 
     def _model_rays(self, cam, n: int, jitter: bool = True):
         """(rays, frame_stride) of frames frame_count .. + n - 1 for the camera model (none set: the pinhole model's)."""
-        name, fov, per_pixel = self._model if self._model is not None else ("pinhole", 180.0, 0)
+        name, fov, per_pixel = self._model or PINHOLE
         aa, radius, focus = self._lens if (self._lens is not None and jitter) else (0.0, 0.0, None)
         lens = radius > 0 and focus is not None
         still = not (aa > 0 or lens)                 # no sample: one set serves every frame
@@ -169,10 +176,40 @@ class InteractiveSession:
         return True
 
     def _lens_cameras(self, cam, n: int) -> np.ndarray:
-        from .host import camera_sequence
         aa, radius, focus = self._lens
         return camera_sequence(cam, self.width, self.height, self.frame_count, n, aa, radius,
                                focus if (radius > 0 and focus is not None) else 0.0)
+
+    def _source(self, cam, n: int, redraw: bool = False, by_count: bool = False) -> tuple:
+        """Where the primary rays of frames frame_count .. + n - 1 come from: ("plain",) -- the tracer's own pinhole
+        rays of ``cam`` --, ("cameras", sequence) or ("rays", buffer, frame_stride), the buffer kept alive in ``_rays``.
+
+        * A redraw is un-jittered: plain under no model or the pinhole model, the model's centre rays otherwise.
+        * A camera model means ray sets.
+        * A lens alone means a camera sequence for frames blended by frame number, and the pinhole model's ray sets
+          for frames blended by each pixel's own count (``by_count``): there is no adaptive call over cameras.
+        * Neither: plain."""
+        if redraw:
+            return ("plain",) if (self._model or PINHOLE)[0] == "pinhole" else ("rays", *self._model_rays(cam, n, jitter=False))
+        if self._model is not None or (by_count and self._lens is not None):
+            return ("rays", *self._model_rays(cam, n))
+        return ("cameras", self._lens_cameras(cam, n)) if self._lens is not None else ("plain",)
+
+    def _issue(self, source: tuple, n: int, by_count: tuple | None = None, *selector):
+        """Frames frame_count .. + n - 1 from ``source`` over the rows of a shard ``selector`` (band, n_shards, shard;
+        left out: the whole image), blended by frame number -- or, with ``by_count`` = (threshold, min_frames), by each
+        pixel's own count, for the pixels still active: the adaptive call's statistics."""
+        kind, *what = source
+        if by_count is None:
+            if kind == "rays":
+                return self.pt.render_rays(self.frame_count, n, *what, *selector)
+            if kind == "cameras":
+                return self.pt.render_cameras(self.frame_count, *what, *selector)
+            return self.pt.render(self.frame_count, n, *selector)   # main.cpp:612-613
+        if kind == "rays":
+            return self.pt.render_rays_adaptive(self.frame_count, n, *what, *by_count, *selector)
+        assert kind == "plain", "no adaptive call over cameras"
+        return self.pt.render_adaptive(self.frame_count, n, *by_count, *selector)
 
     def frame(self, redraw: bool = False, band: int = 1, n_shards: int = 1, shard: int = 0):
         if redraw:                                   # main.cpp:592-596
@@ -181,15 +218,8 @@ class InteractiveSession:
             self._counts_differ = False              # the image starts again: every pixel at one count
         else:                                        # main.cpp:597-601
             depth = self.max_bounce_depth
-        cam = self.camera.uniforms()
-        self.pt.set_frame(self.width, self.height, cam, depth)
-        if self._model is not None and not (redraw and self._model[0] == "pinhole"):
-            rays, stride = self._model_rays(cam, 1, jitter=not redraw)
-            self.pt.render_rays(self.frame_count, 1, rays, stride, band, n_shards, shard)
-        elif self._lens is not None and not redraw:
-            self.pt.render_cameras(self.frame_count, self._lens_cameras(cam, 1), band, n_shards, shard)
-        else:
-            self.pt.render(self.frame_count, 1, band, n_shards, shard)   # main.cpp:612-613
+        cam = self._set_frame(depth)
+        self._issue(self._source(cam, 1, redraw), 1, None, band, n_shards, shard)
         self._remember(cam)
         if not redraw:                               # main.cpp:628
             self.frame_count += 1
@@ -232,13 +262,8 @@ class InteractiveSession:
         stats, done = None, 0
         while done < max_frames:
             n = min(frames_per_call, max_frames - done)
-            cam = self.camera.uniforms()
-            self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
-            if self._model is not None or self._lens is not None:
-                rays, stride = self._model_rays(cam, n)
-                stats = self.pt.render_rays_adaptive(self.frame_count, n, rays, stride, threshold, min_frames)
-            else:
-                stats = self.pt.render_adaptive(self.frame_count, n, threshold, min_frames)
+            cam = self._set_frame(self.max_bounce_depth)
+            stats = self._issue(self._source(cam, n, by_count=True), n, (threshold, min_frames))
             if stats["n_active_pixels"] == 0:        # nothing was rendered: the frames were not issued
                 break
             self._remember(cam)
@@ -258,11 +283,10 @@ class InteractiveSession:
         if self._model is not None and self._model[0] != "pinhole":
             raise ValueError(f"reproject: the {self._model[0]!r} camera model has no reprojection (pinhole views only): "
                              "reproject_view() takes every model")
-        if self.frame_count == 0 or self._rendered_camera is None:
+        if self.frame_count == 0 or self._rendered_view is None:
             raise ValueError("reproject: nothing was rendered yet (frame_count == 0)")
-        cam = self.camera.uniforms()
-        self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
-        stats = self.pt.reproject(self._rendered_camera, **params)
+        cam = self._set_frame(self.max_bounce_depth)
+        stats = self.pt.reproject(self._rendered_view[0], **params)
         self._guide_view = None                      # it left camera-keyed guides of the new view
         self._remember(cam)
         return stats
@@ -279,11 +303,10 @@ class InteractiveSession:
         ``frame_counted()``.  Returns the call's statistics."""
         if self.frame_count == 0 or self._rendered_view is None:
             raise ValueError("reproject_view: nothing was rendered yet (frame_count == 0)")
-        cam = self.camera.uniforms()
-        (cam_a, model_a, fov_a), (_, model_b, fov_b) = self._rendered_view, self._view(cam)
+        (cam_a, model_a, fov_a), (model_b, fov_b, _) = self._rendered_view, self._model or PINHOLE
         if model_a == "pinhole" and model_b == "pinhole":
             return self.reproject(**params)
-        self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
+        cam = self._set_frame(self.max_bounce_depth)
         stats = self.pt.reproject_view((model_a, cam_a, fov_a), (model_b, cam, fov_b), **params)
         self._counts_differ = True                   # frame_counted() continues at every pixel's own count
         self._guide_rays = None                      # (the library made the new view's guides from rays of its own)
@@ -310,28 +333,17 @@ class InteractiveSession:
         frames of a camera model or a lens go through it, so that a disoccluded pixel
         takes the next frame whole."""
         self.pt.enable_moments(True)
-        cam = self.camera.uniforms()
-        self.pt.set_frame(self.width, self.height, cam, self.max_bounce_depth)
-        if self._counts_differ and (self._model is not None or self._lens is not None):
-            # after reproject_view the pixels hold different counts: the frames' rays at every pixel's own weight
-            rays, stride = self._model_rays(cam, n)
-            stats = self.pt.render_rays_adaptive(self.frame_count, n, rays, stride, 0.0, 0xFFFFFFFF)
-            self._remember(cam)
-            self.frame_count += n
-            return stats
-        if self._model is not None or self._lens is not None:
-            if self._model is not None:
-                rays, stride = self._model_rays(cam, n)
-                self.pt.render_rays(self.frame_count, n, rays, stride)
-            else:
-                self.pt.render_cameras(self.frame_count, self._lens_cameras(cam, n))
+        cam = self._set_frame(self.max_bounce_depth)
+        # after reproject_view the pixels hold different counts: the frames' rays at every pixel's own weight
+        source = self._source(cam, n, by_count=self._counts_differ)
+        if self._counts_differ or source == ("plain",):
+            stats = self._issue(source, n, EVERY_PIXEL)
+        else:                                        # by frame number: the statistics of a call with every pixel active
+            self._issue(source, n)
             plan = self.pt.cameras_batch_plan(n)
             npix, ntiles = self.width * self.height, ((self.width + 7) // 8) * ((self.height + 7) // 8)
-            self._remember(cam)
-            self.frame_count += n
-            return {"n_pixels": npix, "n_active_pixels": npix, "n_tiles": ntiles, "n_active_tiles": ntiles,
-                    "frames_per_batch": plan["frames_per_batch"], "n_batches": plan["n_batches"]}
-        stats = self.pt.render_adaptive(self.frame_count, n, 0.0, 0xFFFFFFFF)
+            stats = {"n_pixels": npix, "n_active_pixels": npix, "n_tiles": ntiles, "n_active_tiles": ntiles,
+                     "frames_per_batch": plan["frames_per_batch"], "n_batches": plan["n_batches"]}
         self._remember(cam)
         self.frame_count += n
         return stats
@@ -348,7 +360,6 @@ class InteractiveSession:
         """Tell the device which model vertices ``first`` .. hold: ``mesh``'s model-space records
         (``host.model_records``) are kept there for ``move_model``.  Returns the model's id
         (``PathTracer.define_model``)."""
-        from .host import model_records
         return self.pt.define_model(first, model_records(mesh))
 
     def move_model(self, model_id: int, ops, relight: bool = False):
@@ -356,7 +367,6 @@ class InteractiveSession:
         (``PathTracer.place_models`` -- the matrix goes up, not the vertices), then the depth-1
         redraw frame, as ``edit_vertices``.  ``relight`` when the model is a light whose area
         changes.  Returns ``frame(True)``'s result."""
-        from .host import model_matrix
         self.pt.place_models([(model_id, model_matrix(ops))], relight=relight)
         return self.frame(True)
 
@@ -367,8 +377,6 @@ class InteractiveSession:
         the reference's material panel makes from a combo box of names
         (ImGuiLayer.hpp:37-49): ``pick(x, y)["material_id"]`` names the record
         ``PathTracer.update_materials`` edits.  Changes no image."""
-        from .host import camera_pixel_ray
-        from .tracer import decode_hits
         if not (0 <= px < self.width and 0 <= py < self.height):
             raise ValueError(f"pick: pixel ({px}, {py}) is outside the {self.width}x{self.height} frame")
         ray = camera_pixel_ray(self.camera.uniforms(), px, py, self.width, self.height)
@@ -395,11 +403,20 @@ class InteractiveSession:
             self.pt.render_guides_rays(self._guide_rays)
         self._guide_view = want
 
-    def _guides_for_this_view(self):
-        """Guide images made from rays carry no camera, so the library cannot tell that they belong to another
-        view: the session remembers what it made them for and renders them again when that has changed."""
+    def _filtered(self, run, curable):
+        """The guide images of this view, then the filter ``run``; on the library's stale-guides refusal -- a
+        PNRT_E_STATE whose text ``curable`` accepts -- the guides are rendered and the filter runs once more.
+        Guide images made from rays carry no camera, so the library cannot tell that they belong to another view:
+        the session remembers what it made them for and renders them again when that has changed."""
         if self._guide_want() != self._guide_view:
             self._render_guides()
+        try:
+            run()
+        except PnrtError as e:
+            if getattr(e, "code", 0) != E_STATE or not curable(str(e)):
+                raise
+            self._render_guides()
+            run()
 
     def preview(self, **params):
         """The denoised preview of the accumulation image as it stands (after ``frame()``,
@@ -409,15 +426,7 @@ class InteractiveSession:
         are made from rays and carry no camera, so there the session itself compares the
         view they were made for -- then the image is filtered.  ``params`` are
         ``PathTracer.denoise``'s; read the result with ``PathTracer.read_denoised()``."""
-        from .tracer import PnrtError
-        self._guides_for_this_view()
-        try:
-            self.pt.denoise(**params)
-        except PnrtError as e:
-            if getattr(e, "code", 0) != -3:          # PNRT_E_STATE: no guides yet, or stale ones
-                raise
-            self._render_guides()
-            self.pt.denoise(**params)
+        self._filtered(lambda: self.pt.denoise(**params), lambda text: True)     # its PNRT_E_STATE: no guides yet, or stale ones
 
     def show(self, denoised: bool = False, auto_exposure: bool = False, **display_params) -> np.ndarray:
         """The frame as a screen takes it (main.cpp:618-628's display, converted on the
@@ -428,7 +437,6 @@ class InteractiveSession:
         shown image is taken first and the exposure derived from it
         (``tracer.exposure_from_histogram`` at its defaults), in place of any ``exposure``
         given."""
-        from .tracer import exposure_from_histogram
         source = "denoised" if denoised else "accum"
         if auto_exposure:
             display_params["exposure"] = exposure_from_histogram(self.pt.luma_histogram(source))
@@ -442,12 +450,4 @@ class InteractiveSession:
         alone: only then are they rendered and the filter tried again.  A PNRT_E_STATE
         about the moments (never enabled, or not covering the accumulation) is raised
         with its message."""
-        from .tracer import PnrtError
-        self._guides_for_this_view()
-        try:
-            self.pt.denoise_variance(**params)
-        except PnrtError as e:
-            if getattr(e, "code", 0) != -3 or "render_guides" not in str(e):
-                raise
-            self._render_guides()
-            self.pt.denoise_variance(**params)
+        self._filtered(lambda: self.pt.denoise_variance(**params), lambda text: "render_guides" in text)

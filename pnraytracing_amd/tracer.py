@@ -33,6 +33,38 @@ class PnrtError(RuntimeError):
     pass
 
 
+# ---- marshalling: each rule of the C ABI's Python side once -------------------------------------------------
+def _u32(who, **values):
+    """(ctypes would truncate 2**32 + 5 to 5 without a word)"""
+    for name, v in values.items():
+        if not 0 <= v <= 0xFFFFFFFF:
+            raise ValueError(f"{who}: {name} = {v} is outside 0 .. 2**32 - 1")
+
+
+def _i64(who, **values):
+    for name, v in values.items():
+        if not -2 ** 63 <= v < 2 ** 63:
+            raise ValueError(f"{who}: {name} = {v} does not fit 64 bits")
+
+
+def _camera(uniforms) -> "N.Camera":
+    """The (4, 3) uniforms eye, lower_left, horizontal, vertical as a ``pnrt_camera``."""
+    return N.Camera(*(tuple(map(float, r)) for r in np.asarray(uniforms, np.float32).reshape(4, 3)))
+
+
+def _params(struct, defaults: dict, *given):
+    """A parameter struct by reference, arguments left out at the header's defaults -- or None (NULL: the library's
+    own defaults) when nothing was given."""
+    if all(v is None for v in given):
+        return None
+    return ctypes.byref(struct(*(d if v is None else v for d, v in zip(defaults.values(), given))))
+
+
+def _as_dict(st) -> dict:
+    """A statistics struct's fields (but ``reserved``)."""
+    return {f: getattr(st, f) for f, *_ in st._fields_ if f != "reserved"}
+
+
 class PathTracer:
     def __init__(self, device: int = 0):
         self._lib = N.device_lib()
@@ -181,10 +213,7 @@ class PathTracer:
         self._env_shape = (h, w)
 
     def read_env_table(self) -> np.ndarray:
-        h, w = self._env_shape
-        out = np.empty((h, w, 3), np.float32)
-        self._ck(self._lib.pnrt_read_env_table(self._ctx, N.fptr(out)), "pnrt_read_env_table")
-        return out
+        return self._read_image(self._lib.pnrt_read_env_table, channels=(3,), size=self._env_shape)
 
     def build_bvh(self, tri_bounds: np.ndarray):
         """GPU BuildBVH (pnrt_bvh_build): (nodes (nn, 12) float32, order (n,) int32, max_depth)
@@ -200,9 +229,7 @@ class PathTracer:
         return nodes[:nn.value].copy(), order, md.value
 
     def set_frame(self, width: int, height: int, camera: np.ndarray, max_depth: int = 4):
-        cam = N.Camera()
-        c = np.asarray(camera, np.float32).reshape(4, 3)
-        cam.eye[:], cam.lower_left[:], cam.horizontal[:], cam.vertical[:] = (list(map(float, r)) for r in c)
+        cam = _camera(camera)
         self._ck(self._lib.pnrt_set_frame(self._ctx, width, height, ctypes.byref(cam), max_depth), "pnrt_set_frame")
         self.width, self.height = width, height
 
@@ -232,21 +259,20 @@ class PathTracer:
 
     # ---- frames ----------------------------------------------------------------------
     def render(self, first_frame: int, n_frames: int, band: int = 1, n_shards: int = 1, shard: int = 0):
-        # (ctypes would truncate 2**32 + 5 to 5 without a word)
-        for name, v in (("first_frame", first_frame), ("n_frames", n_frames)):
-            if not 0 <= v <= 0xFFFFFFFF:
-                raise ValueError(f"render: {name} = {v} is outside 0 .. 2**32 - 1")
+        _u32("render", first_frame=first_frame, n_frames=n_frames)
         self._ck(self._lib.pnrt_render(self._ctx, first_frame, n_frames, band, n_shards, shard), "pnrt_render")
 
     def batch_plan(self, n_frames: int, band: int = 1, n_shards: int = 1, shard: int = 0) -> dict:
         """The batches ``render`` would run for such a call at the current frame size
         (pnrt_batch_plan): frames per full batch, number of batches, and the bytes of one
         full batch as PNRT_BATCH_BYTES measures them."""
-        if not 0 <= n_frames <= 0xFFFFFFFF:
-            raise ValueError(f"batch_plan: n_frames = {n_frames} is outside 0 .. 2**32 - 1")
+        return self._plan("batch_plan", n_frames, band, n_shards, shard)
+
+    def _plan(self, which, n_frames, band, n_shards, shard) -> dict:
+        _u32(which, n_frames=n_frames)
         fpb, nb, by = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int64()
-        self._ck(self._lib.pnrt_batch_plan(self._ctx, n_frames, band, n_shards, shard, ctypes.byref(fpb),
-                                           ctypes.byref(nb), ctypes.byref(by)), "pnrt_batch_plan")
+        self._ck(getattr(self._lib, "pnrt_" + which)(self._ctx, n_frames, band, n_shards, shard, ctypes.byref(fpb),
+                                                     ctypes.byref(nb), ctypes.byref(by)), "pnrt_" + which)
         return {"frames_per_batch": fpb.value, "n_batches": nb.value, "batch_bytes": by.value}
 
     def render_cameras(self, first_frame: int, cameras, band: int = 1, n_shards: int = 1, shard: int = 0):
@@ -259,8 +285,7 @@ class PathTracer:
         if cams.dtype != np.float32 or cams.ndim not in (2, 3) or cams.shape[1:] not in ((12,), (4, 3)):
             raise ValueError("render_cameras: cameras must be an (n, 12) or (n, 4, 3) float32 array")
         cams = np.ascontiguousarray(cams).reshape(-1, 12)
-        if not 0 <= first_frame <= 0xFFFFFFFF:
-            raise ValueError(f"render_cameras: first_frame = {first_frame} is outside 0 .. 2**32 - 1")
+        _u32("render_cameras", first_frame=first_frame)
         self._ck(self._lib.pnrt_render_cameras(self._ctx, first_frame, len(cams),
                                                ctypes.cast(cams.ctypes.data, ctypes.POINTER(N.Camera)) if len(cams) else None,
                                                band, n_shards, shard), "pnrt_render_cameras")
@@ -268,17 +293,14 @@ class PathTracer:
     def cameras_batch_plan(self, n_frames: int, band: int = 1, n_shards: int = 1, shard: int = 0) -> dict:
         """``batch_plan`` for a ``render_cameras`` call (pnrt_cameras_batch_plan): the same
         rules with the 48-byte camera-ray record per path counted in ``batch_bytes``."""
-        if not 0 <= n_frames <= 0xFFFFFFFF:
-            raise ValueError(f"cameras_batch_plan: n_frames = {n_frames} is outside 0 .. 2**32 - 1")
-        fpb, nb, by = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int64()
-        self._ck(self._lib.pnrt_cameras_batch_plan(self._ctx, n_frames, band, n_shards, shard, ctypes.byref(fpb),
-                                                   ctypes.byref(nb), ctypes.byref(by)), "pnrt_cameras_batch_plan")
-        return {"frames_per_batch": fpb.value, "n_batches": nb.value, "batch_bytes": by.value}
+        return self._plan("cameras_batch_plan", n_frames, band, n_shards, shard)
 
     # ---- caller ray buffers ---------------------------------------------------------------
     @staticmethod
     def _rays_ptr(rays) -> int:
-        """A device ray buffer as an address: a torch tensor on the device (its data pointer) or an integer."""
+        """A device ray buffer as an address: a torch tensor on the device (its data pointer), an integer, or None (0)."""
+        if rays is None:
+            return 0
         if isinstance(rays, int):
             return rays
         if hasattr(rays, "data_ptr") and hasattr(rays, "is_cuda"):
@@ -298,12 +320,9 @@ class PathTracer:
         serves every frame.  A record with a non-finite float or a zero direction is no ray:
         frame colour 0.  Asynchronous; the buffer is not copied -- keep it unchanged (and
         alive) until the work has completed."""
-        for name, v in (("first_frame", first_frame), ("n_frames", n_frames)):
-            if not 0 <= v <= 0xFFFFFFFF:
-                raise ValueError(f"render_rays: {name} = {v} is outside 0 .. 2**32 - 1")
-        if not -2 ** 63 <= frame_stride < 2 ** 63:
-            raise ValueError(f"render_rays: frame_stride = {frame_stride} does not fit 64 bits")
-        ptr = 0 if rays is None else self._rays_ptr(rays)
+        _u32("render_rays", first_frame=first_frame, n_frames=n_frames)
+        _i64("render_rays", frame_stride=frame_stride)
+        ptr = self._rays_ptr(rays)
         self._ck(self._lib.pnrt_render_rays(self._ctx, first_frame, n_frames, ctypes.c_void_p(ptr), frame_stride, band, n_shards,
                                             shard), "pnrt_render_rays")
 
@@ -312,20 +331,15 @@ class PathTracer:
         (pnrt_render_guides_rays); asynchronous.  The guides carry no camera: ``denoise``,
         ``denoise_variance`` and ``read_aov`` accept them until the frame size, the scene or
         the traversal mode changes or ``render_guides`` / ``reproject`` replaces them."""
-        ptr = 0 if rays is None else self._rays_ptr(rays)
+        ptr = self._rays_ptr(rays)
         self._ck(self._lib.pnrt_render_guides_rays(self._ctx, ctypes.c_void_p(ptr)), "pnrt_render_guides_rays")
 
     @staticmethod
     def ray_camera(model, camera, fov_deg: float = 180.0, aa_width: float = 0.0, lens_radius: float = 0.0,
                    focus_distance: float = 0.0, per_pixel: int = 0, reserved: int = 0) -> "N.RayCamera":
         """A ``pnrt_ray_camera``: ``model`` a name of ``CAM_MODELS`` or its number, ``camera`` the (4, 3) uniforms."""
-        rc = N.RayCamera()
-        rc.model = PathTracer._enum("camera model", N.CAM_MODELS, model)
-        c = np.asarray(camera, np.float32).reshape(4, 3)
-        rc.camera.eye[:], rc.camera.lower_left[:], rc.camera.horizontal[:], rc.camera.vertical[:] = (list(map(float, r)) for r in c)
-        rc.fov_deg, rc.aa_width, rc.lens_radius, rc.focus_distance = fov_deg, aa_width, lens_radius, focus_distance
-        rc.per_pixel, rc.reserved = int(per_pixel), int(reserved)
-        return rc
+        return N.RayCamera(PathTracer._enum("camera model", N.CAM_MODELS, model), _camera(camera), fov_deg, aa_width, lens_radius,
+                           focus_distance, int(per_pixel), int(reserved))
 
     def make_rays(self, model, camera, first_frame: int = 0, n_sets: int = 1, frame_stride: int | None = None, out=None,
                   **params):
@@ -336,9 +350,7 @@ class PathTracer:
         per_pixel).  Returns the buffer: ``out`` when given (a float32 tensor on the device,
         or an integer pointer), else a new float32 tensor of shape (records, 8) -- allocated
         and filled on the wrapped context stream."""
-        for name, v in (("first_frame", first_frame), ("n_sets", n_sets)):
-            if not 0 <= v <= 0xFFFFFFFF:
-                raise ValueError(f"make_rays: {name} = {v} is outside 0 .. 2**32 - 1")
+        _u32("make_rays", first_frame=first_frame, n_sets=n_sets)
         pix = self.width * self.height
         if frame_stride is None:
             frame_stride = pix if n_sets > 1 else 0
@@ -361,22 +373,18 @@ class PathTracer:
         self._ck(self._lib.pnrt_synchronize(self._ctx), "pnrt_synchronize")
 
     def read_accum(self) -> np.ndarray:
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self._lib.pnrt_read_accum(self._ctx, N.fptr(out)), "pnrt_read_accum")
+        return self._read_image(self._lib.pnrt_read_accum)
+
+    def _read_image(self, fn, *args, channels=(4,), dtype=np.float32, size=None) -> np.ndarray:
+        """A (H, W[, C]) image of the frame's size (or ``size``) read through the library's ``fn(ctx, *args, out)``."""
+        out = np.empty((*(size or (self.height, self.width)), *channels), dtype)
+        self._ck(fn(self._ctx, *args, N.u8ptr(out) if dtype is np.uint8 else N.fptr(out)), fn.__name__)
         return out
 
     def accum_ptr(self) -> int:
         return int(self._lib.pnrt_accum_device_ptr(self._ctx) or 0)
 
     # ---- guide images and the denoised preview -------------------------------------------
-    @staticmethod
-    def _aov(name) -> int:
-        if isinstance(name, str):
-            if name not in N.AOV_NAMES:
-                raise ValueError(f"unknown guide image {name!r}: one of {N.AOV_NAMES}")
-            return N.AOV_NAMES.index(name)
-        return int(name)
-
     def render_guides(self):
         """First-hit position / normal / albedo images of the whole frame for the current
         camera, scene and traversal mode (pnrt_render_guides); asynchronous."""
@@ -385,24 +393,16 @@ class PathTracer:
     def read_aov(self, name) -> np.ndarray:
         """One guide image, (H, W, 4) float32, row 0 = bottom: ``"position"`` (w = hit flag),
         ``"normal"`` (w = material id, -1 on a miss) or ``"albedo"`` (w = texture id or -1)."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self._lib.pnrt_read_aov(self._ctx, self._aov(name), N.fptr(out)), "pnrt_read_aov")
-        return out
+        return self._read_image(self._lib.pnrt_read_aov, self._enum("guide image", N.AOV_NAMES, name))
 
     def aov_ptr(self, name) -> int:
-        return int(self._lib.pnrt_aov_device_ptr(self._ctx, self._aov(name)) or 0)
+        return int(self._lib.pnrt_aov_device_ptr(self._ctx, self._enum("guide image", N.AOV_NAMES, name)) or 0)
 
     def denoise(self, levels: int | None = None, sigma_color: float | None = None, sigma_normal: float | None = None,
                 sigma_position: float | None = None):
         """The a-trous preview of the accumulation image into the denoised image
         (pnrt_denoise); asynchronous.  Arguments left out take the library's defaults."""
-        given = (levels, sigma_color, sigma_normal, sigma_position)
-        if all(v is None for v in given):
-            params = None
-        else:
-            d = DENOISE_DEFAULTS
-            p = N.DenoiseParams(*(d[k] if v is None else v for k, v in zip(d, given)))
-            params = ctypes.byref(p)
+        params = _params(N.DenoiseParams, DENOISE_DEFAULTS, levels, sigma_color, sigma_normal, sigma_position)
         self._ck(self._lib.pnrt_denoise(self._ctx, params), "pnrt_denoise")
 
     def denoise_variance(self, levels: int | None = None, sigma_variance: float | None = None,
@@ -411,19 +411,11 @@ class PathTracer:
         (pnrt_denoise_variance); asynchronous.  ``sigma_variance`` counts standard errors of
         the centre pixel, taken from the sample moments, which must cover the accumulation
         (``enable_moments`` before the frames).  Arguments left out take the library's defaults."""
-        given = (levels, sigma_variance, sigma_normal, sigma_position)
-        if all(v is None for v in given):
-            params = None
-        else:
-            d = DENOISE_VARIANCE_DEFAULTS
-            p = N.DenoiseVarianceParams(*(d[k] if v is None else v for k, v in zip(d, given)))
-            params = ctypes.byref(p)
+        params = _params(N.DenoiseVarianceParams, DENOISE_VARIANCE_DEFAULTS, levels, sigma_variance, sigma_normal, sigma_position)
         self._ck(self._lib.pnrt_denoise_variance(self._ctx, params), "pnrt_denoise_variance")
 
     def read_denoised(self) -> np.ndarray:
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self._lib.pnrt_read_denoised(self._ctx, N.fptr(out)), "pnrt_read_denoised")
-        return out
+        return self._read_image(self._lib.pnrt_read_denoised)
 
     def denoised_ptr(self) -> int:
         return int(self._lib.pnrt_denoised_device_ptr(self._ctx) or 0)
@@ -454,9 +446,7 @@ class PathTracer:
     def read_display(self) -> np.ndarray:
         """The display image, (H, W, 4) uint8, alpha 255; top row first unless the last
         ``display`` asked for ``bottom_first`` (pnrt_read_display; synchronises)."""
-        out = np.empty((self.height, self.width, 4), np.uint8)
-        self._ck(self._lib.pnrt_read_display(self._ctx, N.u8ptr(out)), "pnrt_read_display")
-        return out
+        return self._read_image(self._lib.pnrt_read_display, dtype=np.uint8)
 
     def display_ptr(self) -> int:
         return int(self._lib.pnrt_display_device_ptr(self._ctx) or 0)
@@ -504,16 +494,12 @@ class PathTracer:
     def read_moments(self) -> np.ndarray:
         """The moments image, (H, W, 4) float32, row 0 = bottom: mean luminance, M2, 0, and
         the frame count n as uint32 bits (``m[..., 3].view(np.uint32)``)."""
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self._lib.pnrt_read_moments(self._ctx, N.fptr(out)), "pnrt_read_moments")
-        return out
+        return self._read_image(self._lib.pnrt_read_moments)
 
     def read_error(self) -> np.ndarray:
         """The clamped relative standard error of every pixel, (H, W) float32, +inf where
         fewer than two frames were folded in (pnrt_read_error)."""
-        out = np.empty((self.height, self.width), np.float32)
-        self._ck(self._lib.pnrt_read_error(self._ctx, N.fptr(out)), "pnrt_read_error")
-        return out
+        return self._read_image(self._lib.pnrt_read_error, channels=())
 
     def moments_ptr(self) -> int:
         return int(self._lib.pnrt_moments_device_ptr(self._ctx) or 0)
@@ -524,7 +510,7 @@ class PathTracer:
         st = N.ConvergenceStats()
         self._ck(self._lib.pnrt_convergence(self._ctx, ctypes.c_float(threshold), band, n_shards, shard, ctypes.byref(st)),
                  "pnrt_convergence")
-        return _with_mean_error({f: getattr(st, f) for f in CONVERGENCE_FIELDS})
+        return _with_mean_error(_as_dict(st))
 
     def render_adaptive(self, first: int, n: int, threshold: float, min_frames: int = 8, band: int = 1, n_shards: int = 1,
                         shard: int = 0) -> dict:
@@ -534,13 +520,11 @@ class PathTracer:
         the accumulation was last reset.  Waits for the calls in flight, evaluates the mask
         once, then queues the frames like ``render``.  Returns the fields of
         ``pnrt_adaptive_stats``; ``n = 0`` only asks how much is left."""
-        for name, v in (("first", first), ("n", n), ("min_frames", min_frames)):
-            if not 0 <= v <= 0xFFFFFFFF:
-                raise ValueError(f"render_adaptive: {name} = {v} is outside 0 .. 2**32 - 1")
+        _u32("render_adaptive", first=first, n=n, min_frames=min_frames)
         st = N.AdaptiveStats()
         self._ck(self._lib.pnrt_render_adaptive(self._ctx, first, n, ctypes.c_float(threshold), min_frames, band, n_shards,
                                                 shard, ctypes.byref(st)), "pnrt_render_adaptive")
-        return {f: getattr(st, f) for f, _ in st._fields_}
+        return _as_dict(st)
 
     def render_rays_adaptive(self, first: int, n: int, rays, frame_stride: int, threshold: float, min_frames: int = 8,
                              band: int = 1, n_shards: int = 1, shard: int = 0) -> dict:
@@ -549,17 +533,14 @@ class PathTracer:
         buffer rules; the records of inactive pixels do not matter), folded at the weight of
         the pixel's own count.  ``threshold 0, min_frames 0xFFFFFFFF`` makes every pixel
         active.  Returns the fields of ``pnrt_adaptive_stats``."""
-        for name, v in (("first", first), ("n", n), ("min_frames", min_frames)):
-            if not 0 <= v <= 0xFFFFFFFF:
-                raise ValueError(f"render_rays_adaptive: {name} = {v} is outside 0 .. 2**32 - 1")
-        if not -2 ** 63 <= frame_stride < 2 ** 63:
-            raise ValueError(f"render_rays_adaptive: frame_stride = {frame_stride} does not fit 64 bits")
-        ptr = 0 if rays is None else self._rays_ptr(rays)
+        _u32("render_rays_adaptive", first=first, n=n, min_frames=min_frames)
+        _i64("render_rays_adaptive", frame_stride=frame_stride)
+        ptr = self._rays_ptr(rays)
         st = N.AdaptiveStats()
         self._ck(self._lib.pnrt_render_rays_adaptive(self._ctx, first, n, ctypes.c_void_p(ptr), frame_stride,
                                                      ctypes.c_float(threshold), min_frames, band, n_shards, shard, ctypes.byref(st)),
                  "pnrt_render_rays_adaptive")
-        return {f: getattr(st, f) for f, _ in st._fields_}
+        return _as_dict(st)
 
     def reproject(self, from_camera: np.ndarray, normal_min: float | None = None, position_tolerance: float | None = None,
                   max_history: int | None = None) -> dict:
@@ -572,24 +553,18 @@ class PathTracer:
         ``render_adaptive(first >= 1, ...)``, which weighs every pixel by its own count.
         Leaves the guide images valid for the current camera.  Arguments left out take
         the library's defaults.  Returns the fields of ``pnrt_reproject_stats``."""
-        cam = N.Camera()
-        c = np.asarray(from_camera, np.float32).reshape(4, 3)
-        cam.eye[:], cam.lower_left[:], cam.horizontal[:], cam.vertical[:] = (list(map(float, r)) for r in c)
+        cam = _camera(from_camera)
         params = self._reproject_params("reproject", normal_min, position_tolerance, max_history)
         st = N.ReprojectStats()
         self._ck(self._lib.pnrt_reproject(self._ctx, ctypes.byref(cam), params, ctypes.byref(st)), "pnrt_reproject")
-        return {f: getattr(st, f) for f, _ in st._fields_ if f != "reserved"}
+        return _as_dict(st)
 
     @staticmethod
     def _reproject_params(who, normal_min, position_tolerance, max_history):
         """``pnrt_reproject_params`` by reference, or None (the library's defaults) when nothing was given."""
-        given = (normal_min, position_tolerance, max_history)
-        if all(v is None for v in given):
-            return None
-        if max_history is not None and not 0 <= max_history <= 0xFFFFFFFF:
-            raise ValueError(f"{who}: max_history = {max_history} is outside 0 .. 2**32 - 1")
-        d = REPROJECT_DEFAULTS
-        return ctypes.byref(N.ReprojectParams(*(d[k] if v is None else v for k, v in zip(d, given)), 0))
+        if max_history is not None:
+            _u32(who, max_history=max_history)
+        return _params(N.ReprojectParams, REPROJECT_DEFAULTS, normal_min, position_tolerance, max_history)
 
     def reproject_view(self, from_view, to_view, normal_min: float | None = None, position_tolerance: float | None = None,
                        max_history: int | None = None) -> dict:
@@ -608,7 +583,7 @@ class PathTracer:
         st = N.ReprojectStats()
         self._ck(self._lib.pnrt_reproject_view(self._ctx, ctypes.byref(views[0]), ctypes.byref(views[1]), params, ctypes.byref(st)),
                  "pnrt_reproject_view")
-        return {f: getattr(st, f) for f, _ in st._fields_ if f != "reserved"}
+        return _as_dict(st)
 
     def pack_rows(self, dst_ptr: int, band: int, n_shards: int, shard: int):
         self._ck(self._lib.pnrt_pack_rows(self._ctx, ctypes.c_void_p(dst_ptr), band, n_shards, shard), "pnrt_pack_rows")
@@ -622,7 +597,7 @@ class PathTracer:
     def device_info(self) -> dict:
         info = N.DeviceInfo()
         self._ck(self._lib.pnrt_get_device_info(self._ctx, ctypes.byref(info)), "pnrt_get_device_info")
-        return {f: getattr(info, f) for f, _ in info._fields_}
+        return _as_dict(info)
 
     def profile_enable(self, on: bool = True):
         """Bracket every kernel launch with HIP events on the launch stream (resets totals)."""
